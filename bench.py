@@ -1,6 +1,13 @@
 """bench.py -- packet-timesteps per second of the MI355X update_packets engine on the synthetic 50^3 grid.
 
-python bench.py --gpus N --steps K --warmup W
+python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (the headline value, ms_per_step, the
+roofline and kernel figures the timed steps' own event times and counters give).  --dump-outputs DIR then writes
+what the last timed step computed (dump_outputs below).  --full adds every leg that takes runs of its own after
+the timed steps: cpu_baseline and parity_vs_cpu, estimator_allreduce, dropin_host_path, update_grid,
+update_grid_nebular, workload_survey_8d, baseline_configs, timestep_loop, level_mode_5x_lines (--no-cpu-baseline,
+--no-update-grid and --no-extra take legs out of it again).
 
 N>1: one process per GPU.  Under torch.distributed.run (RANK / WORLD_SIZE set) this process is one rank; a bare
 `python bench.py --gpus N` starts the N rank processes itself (before anything touches torch or the GPU), waits for
@@ -506,6 +513,55 @@ def nebular_update_grid(rank, cpu, progress):
     return out
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+DUMP_PACKET_SAMPLE = 50_000
+# the packet fields of a dumped row, in column order (vector fields take one column per component)
+DUMP_PACKET_FIELDS = ("where", "type", "last_cross", "interactions", "nscatterings", "last_event", "pos", "dir",
+                      "e_cmf", "e_rf", "nu_cmf", "nu_rf", "next_trans", "emissiontype", "em_pos", "em_time",
+                      "prop_time", "absorptiontype", "trueemissiontype", "trueem_time", "absorptionfreq",
+                      "absorptiondir", "stokes", "pol_dir", "tdecay", "escape_type", "escape_time", "scat_count",
+                      "number", "originated_from_particlenotgamma", "pellet_decaytype", "pellet_nucindex",
+                      "trueemissionvelocity", "mastate")
+
+
+def dump_outputs(outdir, eng, packets_like, seed=20240607):
+    """What the last timed step left for a caller of the resident path, as outdir/<name>.npy (float64; compton_emiss
+    in its own float32), at most DUMP_BUDGET_BYTES in all:
+      est_<array>: the step's estimators (Engine.download_estimators into zeroed host arrays): J, nuJ, ffheating,
+        colheating, rpkt_emiss, gamma, bfheating, ecounter, acounter, compton_emiss; est_scalars (the scalar
+        estimators in the order of their sorted names) and est_counters (the event counters);
+      packets: a fixed, seeded sample of the packets after the step (Engine.download), one row per packet with the
+        columns of DUMP_PACKET_FIELDS; packet_index: the rows' indices in the ensemble.
+    The ensemble, the model and the sample are seeded, so two builds run with the same arguments dump the same
+    packets.  Returns {name: shape}."""
+    os.makedirs(outdir, exist_ok=True)
+    est = eng.download_estimators()
+    sc = est.scalars()
+    out = {"est_J": est.J, "est_nuJ": est.nuJ, "est_ffheating": est.ffheating, "est_colheating": est.colheating,
+           "est_rpkt_emiss": est.rpkt_emiss, "est_gamma": est.gamma, "est_bfheating": est.bfheating,
+           "est_ecounter": est.ecounter.astype(np.float64), "est_acounter": est.acounter.astype(np.float64),
+           "est_compton_emiss": est.compton_emiss,
+           "est_scalars": np.array([float(sc[k]) for k in sorted(sc)]),
+           "est_counters": est.counters.astype(np.float64)}
+    used = sum(a.nbytes for a in out.values())
+    ncols = sum(int(np.prod(packets_like.dtype[f].shape, dtype=np.int64)) for f in DUMP_PACKET_FIELDS)
+    n = len(packets_like)
+    nsample = min(n, DUMP_PACKET_SAMPLE, (DUMP_BUDGET_BYTES - used) // (8 * (ncols + 1)))
+    if nsample <= 0:
+        raise SystemExit(f"--dump-outputs: the estimators alone ({used} bytes) exceed {DUMP_BUDGET_BYTES} bytes")
+    pk = np.zeros_like(packets_like)
+    eng.download(pk)
+    idx = np.sort(np.random.default_rng(seed).choice(n, size=nsample, replace=False))
+    s = pk[idx]
+    del pk
+    out["packets"] = np.hstack([np.asarray(s[f], dtype=np.float64).reshape(nsample, -1) for f in DUMP_PACKET_FIELDS])
+    out["packet_index"] = idx.astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BUDGET_BYTES
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -518,15 +574,23 @@ def main():
     ap.add_argument("--max-lines", type=int, default=None, help="synthetic atom: line cap (default 100 000)")
     ap.add_argument("--nlevels-per-ion", type=int, default=None, help="synthetic atom: levels per ion (default 400)")
     ap.add_argument("--nts", type=int, default=10)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (estimators, a seeded sample of "
+                         "the packets) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg of the bench line: cpu_baseline and "
+                         "parity_vs_cpu, estimator_allreduce, dropin_host_path, update_grid, update_grid_nebular, "
+                         "workload_survey_8d, baseline_configs, timestep_loop, level_mode_5x_lines")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the cpu_baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle legs")
     ap.add_argument("--no-update-grid", action="store_true",
-                    help="skip the update_grid temperature-solution measurement (artis_gpu_solve_temperatures)")
+                    help="with --full: skip the update_grid temperature-solution measurement "
+                         "(artis_gpu_solve_temperatures)")
     ap.add_argument("--vpkt", type=int, default=0,
                     help="virtual packets (BASELINE config 5, vpkt.cc) with this many observer directions; the "
                          "timestep must lie in the vspec window [10 d, 30 d] (e.g. --nts 30)")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the drop-in host-path timing and the SURVEY §8(d)-sized second workload")
+                    help="with --full: skip the drop-in host-path timing and the SURVEY §8(d)-sized second workload")
     ap.add_argument("--dry-launch", action="store_true",
                     help="bring up the N ranks over gloo without a GPU and print them (tests the launcher)")
     ap.add_argument("--baseline-config", default=None,
@@ -536,6 +600,8 @@ def main():
                          "at --packets per GPU; prints "
                          "them as one JSON line (for per-config profiles)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: only what the headline figure needs
+        args.no_cpu_baseline = args.no_update_grid = args.no_extra = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
@@ -667,6 +733,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, eng, packets)
+        progress(f"outputs of the last timed step written to {args.dump_outputs}")
 
     total_packet_timesteps = world * P * args.steps
     value = total_packet_timesteps / elapsed
@@ -863,6 +933,8 @@ def main():
             "work_per_packet": {k: float(v) / max(P, 1) for k, v in zip(WORK_NAMES, work)},
             "ceiling": ceiling(alg, P, value / world),
         }
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if allreduce is not None:
             line["estimator_allreduce"] = allreduce
         if ugrid is not None:

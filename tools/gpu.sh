@@ -3,8 +3,8 @@
 # time limit, chained with && so that the first failure ends the call:
 #
 #   tools/gpu.sh tests [pytest paths / -k expr ...]  the -m gpu suite (or a selection)    -> $O/gpu_tests.log
-#   tools/gpu.sh bench [bench.py args ...]           one bench line                        -> $O/bench.json
-#   tools/gpu.sh prof [bench.py args ...]            the bench under rocprofv3 --stats     -> $O/prof/, $O/bench_prof.json
+#   tools/gpu.sh bench [bench.py args ...]           one bench line with every leg (--full) -> $O/bench.json
+#   tools/gpu.sh prof [bench.py args ...]            the --full bench under rocprofv3 --stats -> $O/prof/, $O/bench_prof.json
 #   tools/gpu.sh pmc  [bench.py args ...]            FETCH_SIZE / WRITE_SIZE passes (separate runs) summarised by
 #                                                    tools/pmc_summary.py, copied to profiles/pmc_$T_$NAME.json
 #   tools/gpu.sh sq   [bench.py args ...]            one SQ instruction-counter pass       -> $O/sq/
@@ -40,13 +40,13 @@ run_tests() {
 }
 
 run_bench() {
-  timeout -k 10 900 python3 -u bench.py "$@" > "$O/bench.json" 2> "$O/bench.err" && tail -c 400 "$O/bench.json"
+  timeout -k 10 900 python3 -u bench.py --full "$@" > "$O/bench.json" 2> "$O/bench.err" && tail -c 400 "$O/bench.json"
 }
 
 # (the rocpd database is summarised into $O/kernel_stats.csv and removed: gpurun merges at most 64 MiB back)
 run_prof() {
   rm -rf "$O/prof"
-  timeout -k 10 900 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run -- python3 -u bench.py --no-cpu-baseline "$@" \
+  timeout -k 10 900 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run -- python3 -u bench.py --full --no-cpu-baseline "$@" \
     > "$O/bench_prof.json" 2> "$O/bench_prof.err" &&
   python3 tools/rocpd_stats.py "$O/prof/run_results.db" --csv "$O/kernel_stats.csv" && rm -rf "$O/prof"
 }
