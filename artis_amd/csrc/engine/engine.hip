@@ -933,149 +933,10 @@ __global__ void k_pack_counts(const int32_t *ecounter, const int32_t *acounter, 
 }
 
 // ================================================================================================= host side
+#include "engine_state.h"
+#include "host_tables.h"
+
 namespace {
-
-struct Engine {
-  bool initialised = false;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-  std::vector<void *> allocs;
-  Ctx K{};
-  artis_run_params params{};
-  // sizes
-  int npts_model = 0, nelements = 0, maxnions = 0, nions_total = 0, nlines = 0, ngrid = 0, ntstep = 0;
-  int64_t n_est_doubles = 0;  // J..bfheat + scalars
-  int64_t ma_key_stride = 0;          // 16-bit keys per cell block of the macro-atom cache
-  bool ma_cache_ok = true;             // the atomic data fit the cache's record layout (engine_dev.h ma_layout)
-  std::vector<int64_t> h_dbl_off;     // per level: offset (doubles) of its exact sums in the k_marates scratch
-  double *d_marec_scratch = nullptr;  // k_marates output, [position][cell] per level (k_mapack input)
-  // macro-atom key records (DevCells::ma_row / ma_bin): row of each cell (row mode), the cell of each bin
-  int32_t *d_ma_row = nullptr, *d_ma_bin = nullptr, *d_ma_bincell = nullptr;
-  // level mode (DevCells::ma_lptr): pool capacity, record size per level in 128-byte lines (0: never recorded),
-  // the activity histogram of the walks since the last placement, and the placement's bookkeeping
-  uint32_t *d_ma_lptr = nullptr, *d_ma_lhist = nullptr, *d_lvl_ctr = nullptr;
-  const uint32_t *d_rec_lines = nullptr, *d_rl_off = nullptr;
-  uint32_t row_lines = 0;  // pool lines of one whole cell's records (the initial placement)
-  unsigned long long *d_lvl_buckets = nullptr;
-  int2 *d_build_list = nullptr;
-  int64_t build_list_cap = 0;
-  int64_t ma_level_small = 0, ma_level_large = 0;  // the build list's front (small levels) and back (large) parts
-  uint64_t ma_pool_lines = 0;
-  std::vector<uint32_t> h_rec_lines;
-  int64_t ma_build_lds_doubles = 0;
-  bool ma_lhist_ready = false;
-  bool ma_initial_placement = false;  // the current placement had no activity to go by (whole cells)
-  int64_t ma_level_records = 0, ma_level_lines = 0;  // records / pool lines of the current placement
-  // level mode: sampled jumps on pairs that had a record / on all pairs, over the transports before the last placement
-  int64_t ma_acts_cached = 0, ma_acts_total = 0;
-  int64_t marec_scratch_doubles = 0;
-  double *d_estblock = nullptr;
-  int32_t *d_target_ul = nullptr, *d_target_t = nullptr;
-  bool have_cells = false;
-  int cellstate_nts = -1;
-  int cap_nonempty = 0;
-  // cell-state device buffers
-  float *d_cellf = nullptr;  // packed float arrays
-  int16_t *d_thick = nullptr;
-  float *d_abund = nullptr, *d_glp = nullptr, *d_pf = nullptr;
-  double *d_totcool = nullptr, *d_ccion = nullptr, *d_renorm = nullptr;
-  // nebular inputs (device copies, npts_model-indexed) and the NO_LUT integration workspace
-  double *d_nltepops = nullptr, *d_ntdep = nullptr, *d_ntY = nullptr;
-  float *d_rfTR = nullptr, *d_rfW = nullptr, *d_bfest = nullptr, *d_ntprob = nullptr, *d_ntionen = nullptr;
-  QagWs qag{};
-  int32_t *d_bfcol = nullptr;  // bflist index -> element * maxnions + ion (spectra emission columns)
-  int qag_waves = 0;
-  int64_t nbf_est = 0, nbins_est = 0;  // nebular estimator sections of the block (0 when off)
-  int32_t *d_ne_index = nullptr, *d_ne_mgi = nullptr;
-  // packets
-  uint64_t *d_soa = nullptr, *d_aos = nullptr, *d_snapshot = nullptr;
-  int64_t cap_pkts = 0, npkts = 0;
-  bool have_snapshot = false;
-  // wavefront engine (wavefront.h)
-  WaveState W{};
-  uint32_t *h_ctr = nullptr;  // pinned [2][NQUEUES * 2]
-  hipEvent_t ev_round[2] = {nullptr, nullptr};
-  int wave_grid = 2048;
-  bool use_megakernel = false;
-  bool ma_level_coop = false;  // level mode: k_ma makes the jumps without a record itself (else k_ma_exact)
-  Ctx *d_ctx = nullptr;           // device copy of K for the transport kernels
-  int ma_occ = 1;                 // k_ma minimum waves per SIMD (launch bounds): 1 or 8
-  uint32_t *d_binoffs = nullptr;  // exclusive prefix sums of W.bins
-  void *d_scan_tmp = nullptr;
-  size_t scan_tmp_bytes = 0;
-  int64_t last_rounds = 0;
-  // per kernel class (rpkt, ma, kpkt, classify+bookkeeping): summed device time and launch count of the last
-  // transport, from events bracketing every launch
-  std::vector<hipEvent_t> tev;
-  std::vector<int> tev_class;
-  size_t tev_used = 0;
-  double last_kernel_ms[ARTIS_KCLASS_COUNT] = {0};
-  int64_t last_kernel_launches[ARTIS_KCLASS_COUNT] = {0};
-  double last_transport_ms = 0., last_precompute_ms = 0.;
-  int64_t last_work[ARTIS_WORK_COUNT] = {0};
-  // virtual packets (vpkt.h): device accumulators and the spawn buffer (sized per update)
-  int64_t vpkt_cap_param = 0;
-  std::vector<int32_t> h_anumber;  // artis_atomic_tables.elem_anumber
-  std::vector<double> h_ion_ionpot;  // artis_atomic_tables.ion_ionpot (get_mean_binding_energy)
-  double last_nlte_ms = 0.;
-  std::vector<int32_t> h_line_elem;  // artis_atomic_tables.line_elementindex (virtual-packet line masks)
-  double *d_vpkt_spawn = nullptr;
-  uint32_t vpkt_spawn_cap = 0;
-  uint32_t *d_qsnap = nullptr;    // queue count when the current k_rpkt / k_kpkt launch started (vpkt_drain)
-  // spawn sort (DevVpkt::perm): keys / indices in and out, hipcub temp storage, sized for vpkt_spawn_cap
-  uint32_t *d_vkey = nullptr, *d_vkey2 = nullptr, *d_vidx = nullptr, *d_vperm = nullptr;
-  void *d_vsort_tmp = nullptr;
-  size_t vsort_tmp_bytes = 0;
-  uint32_t *h_vcount = nullptr;   // pinned: spawn count before a flush
-  bool vpkt_sort = true;          // ARTIS_VPKT_SORT=0: trace in buffer order
-  uint32_t *h_vfull = nullptr;    // pinned: DevVpkt::full after a launch
-  int64_t vpkt_drains = 0;        // launches resumed after a full spawn buffer (last update_packets)
-  bool r_binned = false;          // bin the R queue by cell before k_rpkt (ARTIS_GPU_R_BIN=1)
-  bool ma_bin_blk = true;         // few cells: block-local M-queue binning (ARTIS_GPU_MA_BIN_BLK=0: per-entry atomics)
-  bool ma_pre_on = true;          // M-queue pre-tickets (WaveState::ma_pre; ARTIS_GPU_MA_PRE=0: gathered by the scatter)
-  bool mf_rec_on = true;          // F-queue records (WaveState::mf_rec; ARTIS_GPU_MF_REC=0: the per-packet pend arrays)
-  bool bin_push_on = true;        // M queue binned by its producers (WaveState::bin_push; ARTIS_GPU_BIN_PUSH=0: k_ma_bin)
-  int rpkt_walk = -1;             // k_rpkt's bounded line walk: -1 by the previous transport's lines per step, 0 off, 1 on
-  bool rpkt_coop = true;          // detailed-bf models: wave-made continuum sums in k_rpkt (ARTIS_GPU_RPKT_COOP=0: per lane)
-  std::vector<hipEvent_t> vev;  // (start, end) pairs around the k_vpkt launches of the last update
-  size_t vev_used = 0;
-  double last_vpkt_ms = 0.;
-  int64_t last_vpkt_work[4] = {0, 0, 0, 0};
-  int64_t last_vpkt_spawns = 0, last_vpkt_traces = 0;
-  // RCCL communicator of this rank (artis_gpu_comm_init) and the packed block it all-reduces
-  ncclComm_t comm = nullptr;
-  int comm_ranks = 0;
-  double *d_redblock = nullptr;
-  double last_te_ms = 0.;
-  std::string last_error;
-};
-Engine G;
-
-#define HIPCHK(x)                                                                             \
-  do {                                                                                        \
-    hipError_t e_ = (x);                                                                      \
-    if (e_ != hipSuccess) {                                                                   \
-      G.last_error = std::string(#x) + ": " + hipGetErrorString(e_);                          \
-      return ARTIS_ERR_HIP;                                                                   \
-    }                                                                                         \
-  } while (0)
-
-template <typename T>
-int dalloc(T **p, size_t count) {
-  if (count == 0) count = 1;
-  HIPCHK(hipMalloc((void **)p, count * sizeof(T)));
-  G.allocs.push_back((void *)*p);
-  return 0;
-}
-template <typename T>
-int dupload(const T **dst, const T *src, size_t count) {
-  T *d = nullptr;
-  if (dalloc(&d, count)) return ARTIS_ERR_HIP;
-  if (count && src) HIPCHK(hipMemcpy(d, src, count * sizeof(T), hipMemcpyHostToDevice));
-  *dst = d;
-  return 0;
-}
 
 // The M-queue bins (DevCells::ma_bin, the cell of each bin ma_bincell) in `order`, and in row mode cell k's
 // records at row k.  Placement never changes a result.
@@ -1091,13 +952,6 @@ int ma_place(const std::vector<int32_t> &order) {
   HIPCHK(hipMemcpy(G.d_ma_bin, bin.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(G.d_ma_bincell, order.data(), n * sizeof(int32_t), hipMemcpyHostToDevice));
   return 0;
-}
-
-// the small-level threshold of the build list (ARTIS_GPU_MA_BUILD_SMALL doubles overrides MA_BUILD_SMALL: tests run
-// both launches on small atoms)
-int64_t ma_build_small() {
-  const char *e = getenv("ARTIS_GPU_MA_BUILD_SMALL");
-  return e ? std::max<int64_t>(0, atoll(e)) : (int64_t)MA_BUILD_SMALL;
 }
 
 // Level mode, every artis_gpu_upload_cellstate: which (cell, level) pairs get a key record (DevCells::ma_lptr) and
@@ -1132,7 +986,7 @@ int ma_level_place() {
   k_lvl_select<<<nb, B, 0, G.stream>>>(G.K, G.d_rec_lines, G.d_rl_off, G.row_lines, G.d_ma_lptr, G.d_lvl_ctr,
                                        G.d_build_list, G.build_list_cap, npairs, bt,
                                        (uint32_t)std::min<uint64_t>(rest, 0xffffffffu), G.ma_pool_lines,
-                                       G.ma_lhist_ready ? 1 : 0, ma_build_small());
+                                       G.ma_lhist_ready ? 1 : 0, G.knob.ma_build_small);
   uint32_t c[4];
   HIPCHK(hipMemcpyAsync(c, G.d_lvl_ctr, sizeof c, hipMemcpyDeviceToHost, G.stream));
   k_lvl_decay<<<nb, B, 0, G.stream>>>(G.d_ma_lhist, npairs);
@@ -1148,7 +1002,7 @@ int ma_level_place() {
 
 // the key records of the current level-mode placement (k_ma_build over the placement's list)
 int ma_level_build(int nts) {
-  const int64_t lds_small = std::min<int64_t>(G.ma_build_lds_doubles, ma_build_small());
+  const int64_t lds_small = std::min<int64_t>(G.ma_build_lds_doubles, G.knob.ma_build_small);
   if (G.ma_level_small > 0)
     k_ma_build<<<(unsigned)std::min<int64_t>(G.ma_level_small, 1 << 16), 64, (size_t)std::max<int64_t>(1, lds_small) * 8,
                  G.stream>>>(G.K, G.d_build_list, (uint32_t)G.ma_level_small, nts);
@@ -1158,12 +1012,6 @@ int ma_level_build(int nts) {
         G.K, G.d_build_list + (G.build_list_cap - G.ma_level_large), (uint32_t)G.ma_level_large, nts);
   HIPCHK(hipGetLastError());
   return 0;
-}
-
-int64_t sum_i32(const int32_t *a, int n) {
-  int64_t s = 0;
-  for (int i = 0; i < n; i++) s += a[i];
-  return s;
 }
 
 int check_kernel_error(const char *what) {
@@ -1176,21 +1024,6 @@ int check_kernel_error(const char *what) {
     return (err[0] == ERR_UNSUPPORTED_TYPE) ? ARTIS_ERR_UNSUPPORTED : ARTIS_ERR_PACKET_FAULT;
   }
   return 0;
-}
-
-// Device allocation with an optional injected failure (ARTIS_GPU_FAIL_ALLOC_ABOVE=<bytes>: any single request
-// above that size fails as out-of-memory) so the error paths can be tested.
-hipError_t dmalloc(void **p, size_t bytes) {
-  *p = nullptr;
-  if (const char *lim = getenv("ARTIS_GPU_FAIL_ALLOC_ABOVE"))
-    if (bytes > (size_t)strtoull(lim, nullptr, 10)) return hipErrorOutOfMemory;
-  return hipMalloc(p, bytes);
-}
-
-template <typename T>
-void dfree(T *&p) {
-  if (p) (void)hipFree((void *)p);
-  p = nullptr;
 }
 
 // packet store + per-packet side state; after this every pointer is null and the capacity zero
@@ -1244,9 +1077,6 @@ int alloc_packets(int64_t n) {
   return 0;
 }
 
-// Event-queue transport (wavefront.h): classify, then rounds of R -> M -> K kernels until both the R and M
-// queues stay empty.  The host learns the queue sizes one round late (pinned async copies), so it never
-// stalls the stream; a round enqueued after the work ran out finds empty queues and costs only its launches.
 // the transport kernels read the context through a pointer to this device copy (physics.h)
 int sync_ctx() {
   HIPCHK(hipStreamSynchronize(G.stream));
@@ -1303,7 +1133,7 @@ __global__ void k_vpkt_keys(const double *__restrict__ spawn, uint32_t cap, uint
 int vpkt_flush() {
   if (!G.K.V.on) return 0;
   uint32_t ns = 0;
-  const bool sort = G.vpkt_sort && G.d_vperm;
+  const bool sort = G.knob.vpkt_sort && G.d_vperm;
   if (sort) {
     // the trace order (DevVpkt::perm): a host round trip for the count, then a radix sort of (cell, nu) keys
     HIPCHK(hipMemcpyAsync(G.h_vcount, G.K.V.spawn_ctr, sizeof(uint32_t), hipMemcpyDeviceToHost, G.stream));
@@ -1328,20 +1158,11 @@ int vpkt_flush() {
     HIPCHK(hipcub::DeviceRadixSort::SortPairs(G.d_vsort_tmp, tb, G.d_vkey, G.d_vkey2, G.d_vidx, G.d_vperm, (int)ns,
                                               0, 32, G.stream));
   }
-  // minimum waves per SIMD the virtual-packet kernel is compiled for (ARTIS_VPKT_OCC = 1, 2 or 3; more waves
-  // hide more of the FP64 and memory latency of the walk at the price of register spills)
-  static const int occ = [] {
-    const char *e = getenv("ARTIS_VPKT_OCC");
-    const int v = e ? atoi(e) : VPKT_OCC_DEFAULT;
-    return (v == 2 || v == 3) ? v : 1;
-  }();
+  // minimum waves per SIMD the virtual-packet kernel is compiled for (ARTIS_VPKT_OCC = 1, 2 or 3)
+  const int occ = G.knob.vpkt_occ;
   // every non-empty cell with a coefficient row: the kernel without the gather walk (whose PF-line prefetch arrays
   // would otherwise set the register allocation of the whole kernel); ARTIS_VPKT_LCONLY=0 forces the general one
-  static const bool lc_ok = [] {
-    const char *e = getenv("ARTIS_VPKT_LCONLY");
-    return !(e && e[0] == '0');
-  }();
-  const bool lc_only = lc_ok && G.K.C.linecoef && G.K.C.linecoef_rows >= G.K.C.n_nonempty;
+  const bool lc_only = G.knob.vpkt_lconly && G.K.C.linecoef && G.K.C.linecoef_rows >= G.K.C.n_nonempty;
   // (at most 4 spectra at the default occupancy: the instance whose loops run over 4 spectra, not 8)
   if (lc_only && occ == 2 && G.K.V.nspectra <= 4)
     k_vpkt<0, 2, 4><<<(unsigned)G.wave_grid, WAVE_BLOCK, 0, G.stream>>>(G.d_ctx, G.W.refill_min);
@@ -1362,13 +1183,23 @@ int vpkt_flush() {
   HIPCHK(hipMemsetAsync(G.K.V.spawn_ctr, 0, 2 * sizeof(uint32_t), G.stream));
   return 0;
 }
+// the spawn buffer and its sort arrays; after this every pointer is null and the capacity zero
+void free_vpkt_spawn() {
+  dfree(G.d_vpkt_spawn);
+  G.vpkt_spawn_cap = 0;
+  G.K.V.spawn = nullptr;
+  G.K.V.cap = 0;
+  for (uint32_t **a : {&G.d_vkey, &G.d_vkey2, &G.d_vidx, &G.d_vperm}) dfree(*a);
+  dfree(G.d_vsort_tmp);
+}
+
 // size the spawn buffer for n packets (artis_vpkt_params.spawn_capacity, default 16 per packet, >= 2^20)
 int vpkt_prepare(int64_t n) {
   if (!G.K.V.on) return 0;
   // default: 16 spawns per packet, at most a quarter of the free HBM (a full buffer is traced and the launch
   // resumed, vpkt_drain), at least 2^20 records and never below the overflow records' count
   int64_t cap = G.vpkt_cap_param > 0 ? G.vpkt_cap_param : std::max<int64_t>(16 * n, 1 << 20);
-  if (G.use_megakernel && G.vpkt_cap_param <= 0) {
+  if (G.knob.use_megakernel && G.vpkt_cap_param <= 0) {
     // the megakernel never parks a packet on a full buffer (only the split kernels resume, vpkt_drain): keep the
     // full 16 spawns per packet, or refuse the launch before it starts instead of overflowing inside it
     size_t freeb = 0, totalb = 0;
@@ -1396,21 +1227,10 @@ int vpkt_prepare(int64_t n) {
   const int64_t overshoot = (int64_t)G.wave_grid * WAVE_BLOCK;
   cap = std::min<int64_t>(cap, (((int64_t)1 << 32) - 1 - overshoot) / std::max(1, G.K.V.nobs));
   if ((uint32_t)cap > G.vpkt_spawn_cap) {
-    dfree(G.d_vpkt_spawn);
-    G.vpkt_spawn_cap = 0;
-    G.K.V.spawn = nullptr;
-    G.K.V.cap = 0;
+    free_vpkt_spawn();
     HIPCHK(dmalloc((void **)&G.d_vpkt_spawn, (size_t)cap * VPKT_SPAWN_WORDS * sizeof(double)));
     G.vpkt_spawn_cap = (uint32_t)cap;
-    const char *so = getenv("ARTIS_VPKT_SORT");
-    G.vpkt_sort = !(so && so[0] == '0');
-    for (uint32_t **a : {&G.d_vkey, &G.d_vkey2, &G.d_vidx, &G.d_vperm}) {
-      dfree(*a);
-      *a = nullptr;
-    }
-    dfree(G.d_vsort_tmp);
-    G.d_vsort_tmp = nullptr;
-    if (G.vpkt_sort) {
+    if (G.knob.vpkt_sort) {
       for (uint32_t **a : {&G.d_vkey, &G.d_vkey2, &G.d_vidx, &G.d_vperm})
         HIPCHK(dmalloc((void **)a, (size_t)cap * sizeof(uint32_t)));
       G.vsort_tmp_bytes = 0;
@@ -1420,7 +1240,7 @@ int vpkt_prepare(int64_t n) {
     }
   }
   if (!G.h_vcount) HIPCHK(hipHostMalloc((void **)&G.h_vcount, sizeof(uint32_t), hipHostMallocDefault));
-  G.K.V.perm = G.vpkt_sort ? G.d_vperm : nullptr;
+  G.K.V.perm = G.knob.vpkt_sort ? G.d_vperm : nullptr;
   G.K.V.spawn = G.d_vpkt_spawn;
   G.K.V.cap = G.vpkt_spawn_cap;
   HIPCHK(hipMemsetAsync(G.K.V.spawn_ctr, 0, 2 * sizeof(uint32_t), G.stream));
@@ -1505,16 +1325,19 @@ int vpkt_collect(const unsigned long long before[8]) {
   return 0;
 }
 
+// Event-queue transport (wavefront.h): classify, then rounds of R -> M -> K kernels until both the R and M
+// queues stay empty.  The host learns the queue sizes one round late (pinned async copies), so it never
+// stalls the stream; a round enqueued after the work ran out finds empty queues and costs only its launches.
 #define WAVE_MAX_ROUNDS 10000000
 int run_wavefront(int64_t n, int nts, double t2) {
   WaveState W = G.W;
   if (!(G.K.C.have_macache && W.ma_binned)) W.ma_tick = nullptr;  // tickets: cached walk over the binned queue
-  if (!W.ma_tick || !G.ma_pre_on) W.ma_pre = nullptr;            // pre-tickets written by the queue's producers
-  if (!G.mf_rec_on) W.mf_rec = nullptr;                           // F-queue records (else pend / pend_jumps / rng_n)
+  if (!W.ma_tick || !G.knob.ma_pre_on) W.ma_pre = nullptr;            // pre-tickets written by the queue's producers
+  if (!G.knob.mf_rec_on) W.mf_rec = nullptr;                           // F-queue records (else pend / pend_jumps / rng_n)
   // the M queue's producers bin it as they append (many cells only: the block-local binning of few-cell models
   // counts in LDS; not with the binned R queue, which uses the same counts array)
-  W.bin_push = W.ma_binned && G.bin_push_on && !G.r_binned && G.K.C.n_nonempty > 0 &&
-               !(G.ma_bin_blk && G.K.C.n_nonempty + 1 <= MA_BIN_LDS);
+  W.bin_push = W.ma_binned && G.knob.bin_push_on && !G.knob.r_binned && G.K.C.n_nonempty > 0 &&
+               !(G.knob.ma_bin_blk && G.K.C.n_nonempty + 1 <= MA_BIN_LDS);
   const unsigned grid = (unsigned)G.wave_grid;
   if (int rc = sync_ctx()) return rc;
   G.tev_used = 0;
@@ -1542,16 +1365,10 @@ int run_wavefront(int64_t n, int nts, double t2) {
       if (int rc = ma_level_place()) return rc;
       if (int rc = ma_level_build(nts)) return rc;
     }
-    // waves per SIMD k_rpkt is compiled for (ARTIS_GPU_RPKT_OCC = 1, 2 or 3).  The r-packet step needs ~300
-    // registers; at 1 wave/SIMD nothing hides its FP64 latency, and forcing 2 (spilling to scratch) measured
-    // 1.80 s -> 1.53 s per bench step on MI355X, so 2 is the default.
-    static const int rpkt_occ = [] {
-      const char *e = getenv("ARTIS_GPU_RPKT_OCC");
-      return (e && (e[0] == '1' || e[0] == '3')) ? e[0] - '0' : 2;
-    }();
+    const int rpkt_occ = G.knob.rpkt_occ;  // waves per SIMD k_rpkt is compiled for (ARTIS_GPU_RPKT_OCC)
     // the R queue binned by cell (ARTIS_GPU_R_BIN=1; default queue order); not with virtual packets, whose resumed
     // launches read parked packets appended to the queue itself
-    W.r_binned = G.r_binned && !G.K.V.on && G.K.C.n_nonempty > 0;
+    W.r_binned = G.knob.r_binned && !G.K.V.on && G.K.C.n_nonempty > 0;
     if (W.r_binned) {
       TSTART(4);
       const int nne = G.K.C.n_nonempty;
@@ -1565,12 +1382,12 @@ int run_wavefront(int64_t n, int nts, double t2) {
     // the per-block estimator accumulator of few-cell models (dynamic LDS, sized only when it is used)
     const size_t est_shm = est_lds_on(G.K) ? EST_LDS_DOUBLES * sizeof(double) : 0;
     // detailed bf estimators (the nebular options): the instance whose continuum sums are made by the whole wave
-    const bool rpkt_coop = G.K.R.detailed_bf && G.K.T.nbf > 0 && G.K.R.do_r_lc && G.rpkt_coop;
+    const bool rpkt_coop = G.K.R.detailed_bf && G.K.T.nbf > 0 && G.K.R.do_r_lc && G.knob.rpkt_coop;
     // the bounded line walk (k_rpkt WALK) when the previous transport's steps scanned more than 8 lines each on
     // average (ARTIS_GPU_RPKT_WALK=1 / 0 forces it on / off)
     const bool rpkt_walk =
-        G.rpkt_walk > 0 ||
-        (G.rpkt_walk < 0 && G.last_work[WK_RPKT_STEPS] > 0 && G.last_work[WK_LINES_SCANNED] > 8 * G.last_work[WK_RPKT_STEPS]);
+        G.knob.rpkt_walk > 0 ||
+        (G.knob.rpkt_walk < 0 && G.last_work[WK_RPKT_STEPS] > 0 && G.last_work[WK_LINES_SCANNED] > 8 * G.last_work[WK_RPKT_STEPS]);
     auto launch_rpkt = [&]() -> int {
       if (rpkt_coop)
         k_rpkt<2, true><<<grid, WAVE_BLOCK, est_shm, G.stream>>>(G.d_ctx, W, G.d_soa, n, nts, t2);
@@ -1602,7 +1419,7 @@ int run_wavefront(int64_t n, int nts, double t2) {
     if (W.ma_binned) {
       const int nne = G.K.C.n_nonempty;
       // few cells: block-local counts (one device atomic per block and bin instead of one per queue entry)
-      const bool blk = G.ma_bin_blk && nne + 1 <= MA_BIN_LDS;
+      const bool blk = G.knob.ma_bin_blk && nne + 1 <= MA_BIN_LDS;
       if (!W.bin_push) {
         HIPCHK(hipMemsetAsync(W.bins, 0, (size_t)(nne + 1) * sizeof(uint32_t), G.stream));
         if (blk)
@@ -1623,23 +1440,16 @@ int run_wavefront(int64_t n, int nts, double t2) {
     HIPCHK(hipMemsetAsync(W.xhead, 0, 8 * sizeof(uint32_t), G.stream));
     TEND(4);
     TSTART(1);
-    // ARTIS_GPU_MA_WAVES=w (default 4): launch only w blocks per CU (w resident waves per SIMD) -- fewer
-    // concurrent walks thrash the caches less; the walk is bound by the memory system, not by latency hiding
-    // (1e7-packet bench: 2 waves 4694 ms, 3: 3761 ms, 4: 3317 ms, 8: 3725 ms; profiles/r02_ab_ma_waves.txt)
-    static const int ma_waves = [] {
-      const char *e = getenv("ARTIS_GPU_MA_WAVES");
-      const int v = e ? atoi(e) : 4;
-      return (v >= 1 && v <= 8) ? v : 4;
-    }();
-    const unsigned ma_grid = ma_waves ? (unsigned)(G.wave_grid / 8 * ma_waves) : grid;
+    // ARTIS_GPU_MA_WAVES=w (default 4): launch only w blocks per CU (w resident waves per SIMD)
+    const unsigned ma_grid = (unsigned)(G.wave_grid / 8 * G.knob.ma_waves);
     if (G.K.C.ma_level_mode)
       // (the whole-cell placement before the first transport covers few of the pairs walked: those walks would
       // take a round per parked jump, so the first transport makes its exact-sum jumps inline)
-      if (G.ma_level_coop || first_placement)
+      if (G.knob.ma_level_coop || first_placement)
         k_ma<4, true, true><<<ma_grid, WAVE_BLOCK, 0, G.stream>>>(G.d_ctx, W, G.d_soa, n, nts);
       else
         k_ma<8, false, true><<<ma_grid, WAVE_BLOCK, 0, G.stream>>>(G.d_ctx, W, G.d_soa, n, nts);
-    else if (G.ma_occ == 8)
+    else if (G.knob.ma_occ == 8)
       k_ma<8, false, false><<<ma_grid, WAVE_BLOCK, 0, G.stream>>>(G.d_ctx, W, G.d_soa, n, nts);
     else
       k_ma<1, false, false><<<ma_grid, WAVE_BLOCK, 0, G.stream>>>(G.d_ctx, W, G.d_soa, n, nts);
@@ -1761,32 +1571,10 @@ int run_wavefront(int64_t n, int nts, double t2) {
 
 }  // namespace
 
-// ============================================================================================== C ABI
-extern "C" {
-
-
-}  // extern "C"
-
 // ============================================================================ update_grid temperature solution
 // artis_gpu_solve_temperatures (include/artis_gpu.h, te_solver.h): every caller array is copied in, the solution
 // is computed for the listed cells and every array is copied back, so cells not listed round-trip unchanged.
 namespace {
-struct DevBufs {
-  std::vector<void *> p;
-  ~DevBufs() {
-    for (void *q : p) (void)hipFree(q);
-  }
-  template <typename T>
-  int get(T **d, size_t count, const T *src) {
-    if (count == 0) count = 1;
-    HIPCHK(hipMalloc((void **)d, count * sizeof(T)));
-    p.push_back((void *)*d);
-    // host-synchronous: a pageable source may be a temporary, and an asynchronous copy queued behind running
-    // kernels would read it after it is gone
-    if (src) HIPCHK(hipMemcpy(*d, src, count * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-  }
-};
 template <typename T>
 int d2h_vec(std::vector<T> &h, const T *d, size_t n) {
   h.assign(n, T());
@@ -1885,11 +1673,7 @@ int artis_gpu_solve_temperatures(const artis_te_tables *tab, const artis_te_para
   }
   // lanes per cell: one per ion for the per-ion collisional-excitation sums of the cooling rate (te_cooling_rates),
   // floor(64 / g) cells per wave (12 ions: 5 cells on 60 lanes); ARTIS_GPU_TE_LANES overrides (1 = one cell per lane)
-  int g = te_lanes_per_cell(ni);
-  if (const char *ev = getenv("ARTIS_GPU_TE_LANES")) {
-    const int v = atoi(ev);
-    if (v >= 1 && v <= 64) g = v;
-  }
+  const int g = G.knob.te_lanes ? G.knob.te_lanes : te_lanes_per_cell(ni);
   const int cpw = 64 / g;
   Ctx *dK = nullptr;
   TeDev *dD = nullptr;
@@ -2546,8 +2330,7 @@ int artis_gpu_update_grid_nlte(const artis_nt_shells *nt, const artis_nlte_param
     rc |= up(&S.ion_binding_ok, binding_ok);
     S.anumber = D.anumber;
     // cells solved together: their matrices (8 n^2 bytes each) within ARTIS_GPU_SF_BATCH_GB (default 8 GiB)
-    double sf_gb = 8.;
-    if (const char *v = getenv("ARTIS_GPU_SF_BATCH_GB")) sf_gb = std::max(0.0, atof(v));
+    const double sf_gb = G.knob.sf_batch_gb;
     sf_batch = (int)std::max<double>(1., std::min<double>(nnl, sf_gb * (double)(1ull << 30) / (8.0 * n * n)));
     h_none.assign(sf_batch, -1.);
     const size_t nbq = (size_t)sf_batch;
@@ -2874,28 +2657,22 @@ int artis_gpu_spectrum(int nnubins, int nprocs, double *spec_flux, double *lc_lu
   for (int nnu = 0; nnu < nnubins; nnu++)
     delta[nnu] = spec_delta_freq(nu_min, dlognu, nnu);
   const size_t nspec = (size_t)nt * nnubins;
+  DevBufs B;  // every step below may fail; the scratch is released (hipFree waits for the stream) on all paths
   double *d = nullptr;
-  HIPCHK(dmalloc((void **)&d, (nspec + 2 * (size_t)nt + nnubins) * sizeof(double)));
+  if (int rc = B.get(&d, nspec + 2 * (size_t)nt + nnubins, (const double *)nullptr)) return rc;
   double *d_spec = d, *d_lc = d + nspec, *d_lccmf = d_lc + nt, *d_delta = d_lccmf + nt;
-  // every step below may fail; the scratch is released on all paths
-  auto run = [&]() -> int {
-    if (int rc = sync_ctx()) return rc;
-    HIPCHK(hipMemsetAsync(d, 0, (nspec + 2 * (size_t)nt) * sizeof(double), G.stream));
-    HIPCHK(hipMemcpyAsync(d_delta, delta.data(), nnubins * sizeof(double), hipMemcpyHostToDevice, G.stream));
-    if (G.npkts > 0)
-      k_spectrum<<<(unsigned)((G.npkts + 255) / 256), 256, 0, G.stream>>>(
-          G.d_ctx, G.d_soa, G.npkts, nt, nnubins, dlognu, d_delta, (double)nprocs, d_spec, d_lc, d_lccmf);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(spec_flux, d_spec, nspec * sizeof(double), hipMemcpyDeviceToHost, G.stream));
-    HIPCHK(hipMemcpyAsync(lc_lum, d_lc, nt * sizeof(double), hipMemcpyDeviceToHost, G.stream));
-    HIPCHK(hipMemcpyAsync(lc_lumcmf, d_lccmf, nt * sizeof(double), hipMemcpyDeviceToHost, G.stream));
-    HIPCHK(hipStreamSynchronize(G.stream));
-    return 0;
-  };
-  const int rc = run();
-  (void)hipStreamSynchronize(G.stream);
-  (void)hipFree(d);
-  return rc;
+  if (int rc = sync_ctx()) return rc;
+  HIPCHK(hipMemsetAsync(d, 0, (nspec + 2 * (size_t)nt) * sizeof(double), G.stream));
+  HIPCHK(hipMemcpyAsync(d_delta, delta.data(), nnubins * sizeof(double), hipMemcpyHostToDevice, G.stream));
+  if (G.npkts > 0)
+    k_spectrum<<<(unsigned)((G.npkts + 255) / 256), 256, 0, G.stream>>>(
+        G.d_ctx, G.d_soa, G.npkts, nt, nnubins, dlognu, d_delta, (double)nprocs, d_spec, d_lc, d_lccmf);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(spec_flux, d_spec, nspec * sizeof(double), hipMemcpyDeviceToHost, G.stream));
+  HIPCHK(hipMemcpyAsync(lc_lum, d_lc, nt * sizeof(double), hipMemcpyDeviceToHost, G.stream));
+  HIPCHK(hipMemcpyAsync(lc_lumcmf, d_lccmf, nt * sizeof(double), hipMemcpyDeviceToHost, G.stream));
+  HIPCHK(hipStreamSynchronize(G.stream));
+  return 0;
 }
 int artis_gpu_spectra(const artis_spectra_request *req, artis_spectra_out *out) {
   if (!G.initialised) return ARTIS_ERR_NOT_INITIALISED;
@@ -2932,61 +2709,56 @@ int artis_gpu_spectra(const artis_spectra_request *req, artis_spectra_out *out) 
   size_t total = nnb;  // delta_freq first
   for (const Sec &x : secs)
     if (x.host) total += x.n;
+  DevBufs B;  // released on every path
   double *d = nullptr;
-  HIPCHK(dmalloc((void **)&d, total * sizeof(double)));
+  if (int rc = B.get(&d, total, (const double *)nullptr)) return rc;
   double *dptr[NSEC];
   size_t off = nnb;
   for (int k = 0; k < NSEC; k++) {
     dptr[k] = secs[k].host ? d + off : nullptr;
     if (secs[k].host) off += secs[k].n;
   }
-  auto run = [&]() -> int {
-    if (int rc = sync_ctx()) return rc;
-    HIPCHK(hipMemsetAsync(d + nnb, 0, (total - nnb) * sizeof(double), G.stream));
-    HIPCHK(hipMemcpyAsync(d, delta.data(), nnb * sizeof(double), hipMemcpyHostToDevice, G.stream));
-    SpecArgs A{};
-    A.nnubins = nnb;
-    A.nprocs = req->nprocs;
-    A.abin = req->abin;
-    A.ntstep = nt;
-    A.proccount = proccount;
-    A.ioncount = ioncount;
-    A.maxnions = G.maxnions;
-    A.nbf = G.K.T.nbf;
-    for (int k = 0; k < 3; k++) A.syn_dir[k] = req->syn_dir[k];
-    A.dlognu = dlognu;
-    A.delta_freq = d;
-    A.bf_col = G.d_bfcol;
-    A.line_elem = G.K.T.line_elem;
-    A.line_ion = G.K.T.line_ion;
-    A.flux = dptr[0];
-    A.emission = dptr[1];
-    A.trueemission = dptr[2];
-    A.absorption = dptr[3];
-    A.sflux = dptr[4];
-    A.semission = dptr[5];
-    A.sabsorption = dptr[6];
-    A.lc = dptr[7];
-    A.lccmf = dptr[8];
-    A.glc = dptr[9];
-    A.glccmf = dptr[10];
-    if (G.npkts > 0)
-      k_spectra<<<(unsigned)((G.npkts + 255) / 256), 256, 0, G.stream>>>(G.d_ctx, G.d_soa, G.npkts, A);
-    HIPCHK(hipGetLastError());
-    std::vector<double> h;
-    for (int k = 0; k < NSEC; k++) {
-      if (!secs[k].host) continue;
-      h.resize(secs[k].n);
-      HIPCHK(hipMemcpyAsync(h.data(), dptr[k], secs[k].n * sizeof(double), hipMemcpyDeviceToHost, G.stream));
-      HIPCHK(hipStreamSynchronize(G.stream));
-      for (size_t j = 0; j < secs[k].n; j++) secs[k].host[j] += h[j];
-    }
-    return 0;
-  };
-  const int rc = run();
-  (void)hipStreamSynchronize(G.stream);
-  (void)hipFree(d);
-  return rc;
+  if (int rc = sync_ctx()) return rc;
+  HIPCHK(hipMemsetAsync(d + nnb, 0, (total - nnb) * sizeof(double), G.stream));
+  HIPCHK(hipMemcpyAsync(d, delta.data(), nnb * sizeof(double), hipMemcpyHostToDevice, G.stream));
+  SpecArgs A{};
+  A.nnubins = nnb;
+  A.nprocs = req->nprocs;
+  A.abin = req->abin;
+  A.ntstep = nt;
+  A.proccount = proccount;
+  A.ioncount = ioncount;
+  A.maxnions = G.maxnions;
+  A.nbf = G.K.T.nbf;
+  for (int k = 0; k < 3; k++) A.syn_dir[k] = req->syn_dir[k];
+  A.dlognu = dlognu;
+  A.delta_freq = d;
+  A.bf_col = G.d_bfcol;
+  A.line_elem = G.K.T.line_elem;
+  A.line_ion = G.K.T.line_ion;
+  A.flux = dptr[0];
+  A.emission = dptr[1];
+  A.trueemission = dptr[2];
+  A.absorption = dptr[3];
+  A.sflux = dptr[4];
+  A.semission = dptr[5];
+  A.sabsorption = dptr[6];
+  A.lc = dptr[7];
+  A.lccmf = dptr[8];
+  A.glc = dptr[9];
+  A.glccmf = dptr[10];
+  if (G.npkts > 0)
+    k_spectra<<<(unsigned)((G.npkts + 255) / 256), 256, 0, G.stream>>>(G.d_ctx, G.d_soa, G.npkts, A);
+  HIPCHK(hipGetLastError());
+  std::vector<double> h;
+  for (int k = 0; k < NSEC; k++) {
+    if (!secs[k].host) continue;
+    h.resize(secs[k].n);
+    HIPCHK(hipMemcpyAsync(h.data(), dptr[k], secs[k].n * sizeof(double), hipMemcpyDeviceToHost, G.stream));
+    HIPCHK(hipStreamSynchronize(G.stream));
+    for (size_t j = 0; j < secs[k].n; j++) secs[k].host[j] += h[j];
+  }
+  return 0;
 }
 
 int artis_gpu_vpkt_init(const artis_vpkt_params *vp) {
@@ -3051,11 +2823,12 @@ int artis_gpu_vpkt_init(const artis_vpkt_params *vp) {
     delta_freq[m] = (float)(exp(log(vp->numin_vspec) + ((m + 1) * (V.dlognu))) - lower);
   }
   const std::vector<int32_t> &anum = G.h_anumber;
+  DevBufs B;  // the new parameter set: replaces its predecessor (Engine::mem_vpkt) once it is complete
   int rc = 0;
-  rc |= dupload(&V.obs, obs.data(), obs.size());
-  rc |= dupload(&V.delta_t, delta_t.data(), delta_t.size());
-  rc |= dupload(&V.delta_freq, delta_freq.data(), delta_freq.size());
-  rc |= dupload(&V.anumber, anum.data(), anum.size());
+  rc |= dupload(B, &V.obs, obs.data(), obs.size());
+  rc |= dupload(B, &V.delta_t, delta_t.data(), delta_t.size());
+  rc |= dupload(B, &V.delta_freq, delta_freq.data(), delta_freq.size());
+  rc |= dupload(B, &V.anumber, anum.data(), anum.size());
   {
     // per line, the spectra whose optical depth its opacity enters (vpkt.cc:283-294: exclude -1 drops every
     // line, exclude Z the lines of element Z); padded for the walk's 16-line windows
@@ -3068,21 +2841,23 @@ int artis_gpu_vpkt_init(const artis_vpkt_params *vp) {
         if (V.exclude[ind] != -1 && (an != V.exclude[ind])) m |= (uint8_t)(1u << ind);
       mask[li] = m;
     }
-    rc |= dupload(&V.line_mask, mask.data(), mask.size());
+    rc |= dupload(B, &V.line_mask, mask.data(), mask.size());
   }
   V.vstokes_stride = (int64_t)vp->vmtbins * vp->nobs * vp->nspectra * vp->vmnubins;
   V.vgrid_stride = (vp->vgrid_flag == 1) ? (int64_t)vp->ny_vgrid * vp->nz_vgrid * vp->nrange_grid * vp->nobs : 0;
-  rc |= dalloc(&V.vstokes, (size_t)(3 * V.vstokes_stride));
-  rc |= dalloc(&V.vgrid, (size_t)std::max<int64_t>(3 * V.vgrid_stride, 1));
-  rc |= dalloc(&V.ctr, 8);
-  rc |= dalloc(&V.spawn_ctr, 2);
+  rc |= dalloc(B, &V.vstokes, (size_t)(3 * V.vstokes_stride));
+  rc |= dalloc(B, &V.vgrid, (size_t)std::max<int64_t>(3 * V.vgrid_stride, 1));
+  rc |= dalloc(B, &V.ctr, 8);
+  rc |= dalloc(B, &V.spawn_ctr, 2);
   V.ovf_cap = (uint32_t)((int64_t)G.wave_grid * WAVE_BLOCK);
-  rc |= dalloc(&V.ovf, (size_t)V.ovf_cap * VPKT_SPAWN_WORDS);
-  rc |= dalloc(&V.ovf_ctr, 1);
-  rc |= dalloc(&V.full, 1);
+  rc |= dalloc(B, &V.ovf, (size_t)V.ovf_cap * VPKT_SPAWN_WORDS);
+  rc |= dalloc(B, &V.ovf_ctr, 1);
+  rc |= dalloc(B, &V.full, 1);
   if (!G.d_qsnap) rc |= dalloc(&G.d_qsnap, 1);
   if (!G.h_vfull) HIPCHK(hipHostMalloc((void **)&G.h_vfull, sizeof(uint32_t), hipHostMallocDefault));
   if (rc) return ARTIS_ERR_HIP;
+  G.mem_vpkt.release();
+  G.mem_vpkt.p.swap(B.p);
   V.spawn = G.d_vpkt_spawn;
   V.cap = G.vpkt_spawn_cap;
   V.on = 1;
@@ -3189,20 +2964,18 @@ int artis_gpu_last_work_counts(int64_t out[ARTIS_WORK_COUNT]) {
   return 0;
 }
 
+// Releases whatever the engine holds -- after a complete init, a failed one or none -- and leaves it
+// default-constructed.  Makes no HIP call when nothing is held.
 void artis_gpu_finalize(void) {
-  if (!G.initialised) return;
   artis_gpu_comm_finalize();
-  dfree(G.d_redblock);
-  for (void *p : G.allocs) (void)hipFree(p);
-  G.allocs.clear();
+  G.mem.release();
+  G.mem_vpkt.release();
+  G.mem_gamma.release();
   free_packets();
-  if (G.h_ctr) (void)hipHostFree(G.h_ctr);
-  if (G.h_vfull) (void)hipHostFree(G.h_vfull);
-  if (G.d_vpkt_spawn) (void)hipFree(G.d_vpkt_spawn);
-  for (uint32_t *a : {G.d_vkey, G.d_vkey2, G.d_vidx, G.d_vperm})
-    if (a) (void)hipFree(a);
-  if (G.d_vsort_tmp) (void)hipFree(G.d_vsort_tmp);
-  if (G.h_vcount) (void)hipHostFree(G.h_vcount);
+  free_vpkt_spawn();
+  dfree(G.d_redblock);
+  for (uint32_t *h : {G.h_ctr, G.h_vfull, G.h_vcount})
+    if (h) (void)hipHostFree(h);
   for (hipEvent_t e : G.vev) (void)hipEventDestroy(e);
   for (hipEvent_t e : G.tev) (void)hipEventDestroy(e);
   for (int r = 0; r < 2; r++)
@@ -3236,13 +3009,11 @@ static const char *unsupported_run_param(const artis_run_params *rp) {
   return nullptr;
 }
 
-int artis_gpu_init(int device, const artis_atomic_tables *a, const artis_geometry *g, const artis_run_params *rp) {
-  if (!a || !g || !rp) return ARTIS_ERR_BAD_ARGUMENT;
-  if (const char *why = unsupported_run_param(rp)) {
-    G.last_error = why;
-    return ARTIS_ERR_UNSUPPORTED;
-  }
-  if (G.initialised) artis_gpu_finalize();
+// ---------------------------------------------------------------------------------- artis_gpu_init, by stage
+// Every stage returns an error code; artis_gpu_init releases whatever the stages before it made when one fails.
+
+// What can be refused from the arguments alone (after unsupported_run_param).  Runs before any HIP call.
+static int validate_init(const artis_atomic_tables *a, const artis_geometry *g, const artis_run_params *rp) {
   if (g->grid_type != ARTIS_GRID_UNIFORM && g->grid_type != ARTIS_GRID_SPHERICAL1D) {
     G.last_error = "grid_type must be GRID_UNIFORM or GRID_SPHERICAL1D";
     return ARTIS_ERR_UNSUPPORTED;
@@ -3261,6 +3032,23 @@ int artis_gpu_init(int device, const artis_atomic_tables *a, const artis_geometr
       return ARTIS_ERR_BAD_ARGUMENT;
     }
   }
+  if (rp->excitation_temperature != ARTIS_TEXC_TJ && rp->excitation_temperature != ARTIS_TEXC_TE) {
+    G.last_error = "artis_run_params.excitation_temperature must be ARTIS_TEXC_TJ or ARTIS_TEXC_TE";
+    return ARTIS_ERR_BAD_ARGUMENT;
+  }
+  if (rp->comp_est && (rp->emiss_max < 1 || rp->emiss_max > ARTIS_EMISS_MAX)) {
+    G.last_error = "artis_run_params.emiss_max must be in [1, ARTIS_EMISS_MAX] with comp_est (input.cc:1821-1824)";
+    return ARTIS_ERR_BAD_ARGUMENT;
+  }
+  if ((rp->nlte_pops_on && (!a->ion_nlevels_nlte || !a->ion_first_nlte || a->total_nlte_levels < 0)) ||
+      (rp->multibin_radfield && (a->radfield_nbins <= 0 || !a->radfield_nu_upper)) || rp->nt_max_auger_electrons < 0) {
+    G.last_error = "nebular run parameters without the atomic tables they need (ion_nlevels_nlte / radfield bins)";
+    return ARTIS_ERR_BAD_ARGUMENT;
+  }
+  return 0;
+}
+
+static int create_stream_and_events(int device) {
   G.device = device;
   HIPCHK(hipSetDevice(device));
   HIPCHK(hipStreamCreateWithFlags(&G.stream, hipStreamNonBlocking));
@@ -3269,53 +3057,23 @@ int artis_gpu_init(int device, const artis_atomic_tables *a, const artis_geometr
   HIPCHK(hipEventCreate(&G.ev2));
   for (int r = 0; r < 2; r++) HIPCHK(hipEventCreateWithFlags(&G.ev_round[r], hipEventDisableTiming));
   HIPCHK(hipHostMalloc((void **)&G.h_ctr, 2 * NQUEUES * 2 * sizeof(uint32_t), hipHostMallocDefault));
-  {
-    int ncu = 256;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
-    G.wave_grid = ncu * 8;  // 32 waves per CU of 256-thread blocks; late blocks find the queue drained
-    // (tests: ARTIS_GPU_WAVE_GRID=<blocks>, a multiple of 8, shrinks the persistent grids and the vpkt overflow records)
-    if (const char *wg = getenv("ARTIS_GPU_WAVE_GRID")) G.wave_grid = std::max(8, atoi(wg) / 8 * 8);
-    const char *eng = getenv("ARTIS_GPU_ENGINE");
-    G.use_megakernel = eng && std::string(eng) == "mega";
-    // cell binning of the macro-atom queue (measured 5-15 % faster walks: lanes of a wave share a cell's
-    // records) is on; per-XCD queue ranges measured neutral-to-negative and are off unless asked for
-    const char *b = getenv("ARTIS_GPU_MA_BIN");
-    G.W.ma_binned = !(b && b[0] == '0');
-    // cell binning of the R queue before k_rpkt: measured no faster k_rpkt (1114 vs 1106 ms per bench step) and
-    // ~250 ms more binning per step (profiles/r03g_ab.txt), so off unless asked for (ARTIS_GPU_R_BIN=1)
-    const char *rb = getenv("ARTIS_GPU_R_BIN");
-    G.r_binned = rb && rb[0] == '1';
-    const char *rw = getenv("ARTIS_GPU_RPKT_WALK");
-    G.rpkt_walk = rw ? (rw[0] == '1' ? 1 : 0) : -1;
-    const char *rc_ = getenv("ARTIS_GPU_RPKT_COOP");
-    G.rpkt_coop = !(rc_ && rc_[0] == '0');
-    const char *mp = getenv("ARTIS_GPU_MA_PRE");
-    G.ma_pre_on = !(mp && mp[0] == '0');
-    const char *mf = getenv("ARTIS_GPU_MF_REC");
-    G.mf_rec_on = !(mf && mf[0] == '0');
-    const char *bp = getenv("ARTIS_GPU_BIN_PUSH");
-    G.bin_push_on = !(bp && bp[0] == '0');
-    const char *bb = getenv("ARTIS_GPU_MA_BIN_BLK");
-    G.ma_bin_blk = !(bb && bb[0] == '0');
-    const char *xr = getenv("ARTIS_GPU_MA_XCD");
-    G.W.ma_ranges = (xr && xr[0] == '1') ? 8 : 1;
-    const char *rf = getenv("ARTIS_GPU_REFILL");
-    G.W.refill_min = rf ? std::max(1, std::min(64, atoi(rf))) : 32;
-    // k_ma refills from one coalesced ticket read, so it refills early (1e7-packet bench, before tickets:
-    // 32 idle lanes 2212 ms, 16: 2064 ms, 8: 2042 ms; round 5, with the line-0 suffix and the F-queue records:
-    // 4: 2578 ms, 8: 1694, 12: 1559, 14: 1568, 16: 1581, 20: 1617, 24: 1659; profiles/r5s_refill_sweep.txt)
-    const char *rfm = getenv("ARTIS_GPU_REFILL_MA");
-    G.W.refill_ma = rfm ? std::max(1, std::min(64, atoi(rfm))) : 12;
-    const char *oc = getenv("ARTIS_GPU_MA_OCC");
-    G.ma_occ = (oc && oc[0] == '8') ? 8 : 1;
-    const char *cm = getenv("ARTIS_GPU_MA_COOP_MAX");
-    G.W.coop_max = cm ? std::max(1, std::min(64, atoi(cm))) : 64;
-    // level mode: the jumps without a record made inline by k_ma's wave (ARTIS_GPU_MA_LEVEL_COOP=1), or parked
-    // for k_ma_exact (default: k_ma keeps the row kernel's register budget)
-    const char *lc = getenv("ARTIS_GPU_MA_LEVEL_COOP");
-    G.ma_level_coop = lc && lc[0] == '1';
-  }
-  G.params = *rp;
+  return 0;
+}
+
+// the environment knobs of this engine (engine_state.h) and what follows from them alone
+static void apply_knobs() {
+  G.knob = read_knobs();
+  int ncu = 256;
+  (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, G.device);
+  G.wave_grid = G.knob.wave_grid ? G.knob.wave_grid : ncu * 8;
+  G.W.ma_binned = G.knob.ma_binned;
+  G.W.ma_ranges = G.knob.ma_ranges;
+  G.W.refill_min = G.knob.refill_min;
+  G.W.refill_ma = G.knob.refill_ma;
+  G.W.coop_max = G.knob.coop_max;
+}
+
+static int upload_atomic_tables(const artis_atomic_tables *a, const artis_run_params *rp, const MaTables &ma) {
   G.h_anumber.assign(a->nelements, 0);
   if (a->elem_anumber) G.h_anumber.assign(a->elem_anumber, a->elem_anumber + a->nelements);
   G.h_ion_ionpot.assign(a->nions_total, 0.);
@@ -3379,7 +3137,7 @@ int artis_gpu_init(int device, const artis_atomic_tables *a, const artis_geometr
   {
     std::vector<double> nu8((size_t)(nli + 15) / 16 * 16 + 16, 0.);  // (padded for 16-line windows, k_vpkt)
     std::copy(a->line_nu, a->line_nu + nli, nu8.begin());
-    rc |= dupload(&T.line_nu8, nu8.data(), nu8.size());
+    rc |= dupload(&T.line_nu8, nu8);
   }
   rc |= dupload(&T.line_A, a->line_einstein_A, nli);
   rc |= dupload(&T.line_f, a->line_osc_strength, nli);
@@ -3390,170 +3148,23 @@ int artis_gpu_init(int device, const artis_atomic_tables *a, const artis_geometr
   rc |= dupload(&T.line_upper, a->line_upperlevelindex, nli);
   rc |= dupload(&T.line_lower, a->line_lowerlevelindex, nli);
   rc |= dupload(&T.line_forbidden, a->line_forbidden, nli);
-  // per-line Sobolev coefficients, evaluated on the host with the same expression as rpkt.cc:179-181
-  std::vector<LineTau> lt(nli);
-  for (int li = 0; li < nli; li++) {
-    const int e = a->line_elementindex[li], i = a->line_ionindex[li];
-    const int off = a->ion_uniqueleveloffset[a->elem_uniqueionoffset[e] + i];
-    const int ulo = off + a->line_lowerlevelindex[li], uup = off + a->line_upperlevelindex[li];
-    const double nu_trans = a->line_nu[li];
-    const double A_ul = a->line_einstein_A[li];
-    const double B_ul = ARTIS_CLIGHTSQUAREDOVERTWOH / pow(nu_trans, 3) * A_ul;
-    const double B_lu = (double)a->level_stat_weight[uup] / (double)a->level_stat_weight[ulo] * B_ul;
-    lt[li] = {nu_trans, B_ul, B_lu, ulo, uup};
-  }
-  rc |= dupload(&T.line_tau, lt.data(), nli);
-  // macro-atom per-line constants (macroatom.cc:518-522, 563-566; radfield.h:47; macroatom.h:93,130)
-  std::vector<LineMA> lm(nli);
-  for (int li = 0; li < nli; li++) {
-    const int ulo = lt[li].ul_lower, uup = lt[li].ul_upper;
-    const double epsilon_trans = a->level_epsilon[uup] - a->level_epsilon[ulo];
-    const double nu_trans = epsilon_trans / ARTIS_H;
-    const double A_ul = a->line_einstein_A[li];
-    const double B_ul = ARTIS_CLIGHTSQUAREDOVERTWOH / pow(nu_trans, 3) * A_ul;
-    const double B_lu = (double)a->level_stat_weight[uup] / (double)a->level_stat_weight[ulo] * B_ul;
-    lm[li] = {B_ul, B_lu, pow(nu_trans, 3), pow(ARTIS_H_IONPOT / epsilon_trans, 2)};
-  }
-  rc |= dupload(&T.line_ma, lm.data(), nli);
+  if (rc) return ARTIS_ERR_HIP;
   {
-    // packed collisional-excitation terms (TeExcItem) indexed like uptrans_lineindex
-    size_t nitems = 0;
-    for (int ul = 0; ul < nl; ul++)
-      nitems = std::max(nitems, (size_t)a->level_uptrans_offset[ul] + (size_t)a->level_nuptrans[ul]);
-    std::vector<TeExcItem> items(std::max<size_t>(nitems, 1));
-    for (int ui = 0; ui < a->nions_total; ui++) {
-      const int ul0 = a->ion_uniqueleveloffset[ui];
-      for (int l = 0; l < a->ion_nlevels[ui]; l++) {
-        const int ul = ul0 + l;
-        for (int ii = 0; ii < a->level_nuptrans[ul]; ii++) {
-          const int j = a->level_uptrans_offset[ul] + ii;
-          const int li = a->uptrans_lineindex[j];
-          const int uu = ul0 + a->line_upperlevelindex[li];
-          TeExcItem &x = items[j];
-          x.epsilon_trans = a->level_epsilon[uu] - a->level_epsilon[ul];
-          x.P2 = lm[li].P2;
-          x.coll_str = a->line_coll_str[li];
-          x.osc_f = a->line_osc_strength[li];
-          x.upper_sw = a->level_stat_weight[uu];
-          x.forbidden = a->line_forbidden[li];
-        }
-      }
-    }
-    rc |= dupload(&T.exc_items, items.data(), items.size());
+    const LineTables lt = derive_line_tables(a);
+    rc |= dupload(&T.line_tau, lt.tau.data(), nli);
+    rc |= dupload(&T.line_ma, lt.ma.data(), nli);
+    rc |= dupload(&T.exc_items, lt.exc);
+    rc |= dupload(&T.ma_down, lt.down);
+    rc |= dupload(&T.ma_up, lt.up);
   }
-  {
-    // k_marates' packed transition items (MaDownItem / MaUpItem) indexed like downtrans_lineindex / uptrans_lineindex
-    size_t nd_items = 1, nu_items = 1;
-    for (int ul = 0; ul < nl; ul++) {
-      nd_items = std::max(nd_items, (size_t)a->level_downtrans_offset[ul] + (size_t)a->level_ndowntrans[ul]);
-      nu_items = std::max(nu_items, (size_t)a->level_uptrans_offset[ul] + (size_t)a->level_nuptrans[ul]);
-    }
-    std::vector<MaDownItem> di(nd_items);
-    std::vector<MaUpItem> ui_(nu_items);
-    for (int ui = 0; ui < a->nions_total; ui++) {
-      const int ul0 = a->ion_uniqueleveloffset[ui];
-      for (int l = 0; l < a->ion_nlevels[ui]; l++) {
-        const int ul = ul0 + l;
-        for (int j = 0; j < a->level_ndowntrans[ul]; j++) {
-          const int li = a->downtrans_lineindex[a->level_downtrans_offset[ul] + j];
-          const int lo = a->line_lowerlevelindex[li];
-          MaDownItem &x = di[a->level_downtrans_offset[ul] + j];
-          x = MaDownItem{};
-          x.lower = lo;
-          x.forbidden = a->line_forbidden[li];
-          x.A = a->line_einstein_A[li];
-          x.coll = a->line_coll_str[li];
-          x.osc_f = a->line_osc_strength[li];
-          x.lower_sw = a->level_stat_weight[ul0 + lo];
-          x.eps_target = a->level_epsilon[ul0 + lo];
-          x.B_ul = lm[li].B_ul;
-          x.B_lu = lm[li].B_lu;
-          x.P2 = lm[li].P2;
-        }
-        for (int j = 0; j < a->level_nuptrans[ul]; j++) {
-          const int li = a->uptrans_lineindex[a->level_uptrans_offset[ul] + j];
-          const int up = a->line_upperlevelindex[li];
-          MaUpItem &x = ui_[a->level_uptrans_offset[ul] + j];
-          x = MaUpItem{};
-          x.upper = up;
-          x.forbidden = a->line_forbidden[li];
-          x.coll = a->line_coll_str[li];
-          x.osc_f = a->line_osc_strength[li];
-          x.upper_sw = a->level_stat_weight[ul0 + up];
-          x.eps_upper = a->level_epsilon[ul0 + up];
-          x.B_ul = lm[li].B_ul;
-          x.B_lu = lm[li].B_lu;
-          x.nu3 = lm[li].nu3;
-          x.P2 = lm[li].P2;
-        }
-      }
-    }
-    rc |= dupload(&T.ma_down, di.data(), di.size());
-    rc |= dupload(&T.ma_up, ui_.data(), ui_.size());
-  }
-  // macro-atom records per level (engine_dev.h DevCells::ma_rec): recombination targets are the ionising levels
-  // of the lower ion for levels l <= maxrecombininglevel of ions i > 0 (macroatom.cc:104-124); up-higher targets
-  // are the phixs targets of ionising levels of non-top ions (get_nphixstargets)
-  std::vector<MaMeta> mm(nl);
-  std::vector<int64_t> dbl_off(nl + 1, 0);  // exact-sum scratch of k_marates (doubles, unpadded)
-  int64_t marec = 0;
-  bool ma_cache_ok = true;  // every level's same-ion arrays fit the two-level record layout
-  for (int e = 0; e < ne; e++)
-    for (int i = 0; i < a->elem_nions[e]; i++) {
-      const int ui = a->elem_uniqueionoffset[e] + i;
-      for (int l = 0; l < a->ion_nlevels[ui]; l++) {
-        const int ul = a->ion_uniqueleveloffset[ui] + l;
-        MaMeta &m = mm[ul];
-        m.nr = (i > 0 && l <= a->ion_maxrecombininglevel[ui]) ? a->ion_ionisinglevels[ui - 1] : 0;
-        m.nt = (i < a->elem_nions[e] - 1 && l < a->ion_ionisinglevels[ui]) ? a->level_nphixstargets[ul] : 0;
-        m.nd = a->level_ndowntrans[ul];
-        m.nu = a->level_nuptrans[ul];
-        m.doff = a->level_downtrans_offset[ul];
-        m.uoff = a->level_uptrans_offset[ul];
-        m.base_lower = (i > 0) ? a->ion_uniqueleveloffset[ui - 1] : -1;
-        m.rec_off = (int32_t)marec;
-        const int64_t len = ARTIS_MA_ACTION_COUNT + 2 * (int64_t)m.nd + m.nu + 2 * (int64_t)m.nr + m.nt;
-        // high then low key halves (engine_dev.h ma_layout), records 128-byte aligned
-        marec += (2 * (int64_t)ma_layout(m.nd, m.nu, m.nr, m.nt).hot + 63) / 64 * 64;
-        dbl_off[ul + 1] = len;
-        if (!ma_layout_ok(m.nd, m.nu)) ma_cache_ok = false;
-      }
-    }
-  rc |= dupload(&T.ma_meta, mm.data(), nl);
-  {
-    std::vector<MaWalk> mw(nl);
-    for (int ul = 0; ul < nl; ul++)
-      if (!ma_walk_make(mm[ul], &mw[ul])) ma_cache_ok = false;
-    rc |= dupload(&T.ma_walk, mw.data(), nl);
-  }
-  for (int ul = 0; ul < nl; ul++) dbl_off[ul + 1] += dbl_off[ul];
-  rc |= dupload(&T.ma_dbl_off, dbl_off.data(), nl + 1);
-  G.h_dbl_off = dbl_off;
-  {
-    // internal same-ion jump targets in the (reference) order of their cumulative arrays
-    std::vector<int2> dt(std::max<int64_t>(ndown, 1)), ut(std::max<int64_t>(nup, 1));
-    for (int e = 0; e < ne; e++)
-      for (int i = 0; i < a->elem_nions[e]; i++) {
-        const int ui = a->elem_uniqueionoffset[e] + i;
-        const int base = a->ion_uniqueleveloffset[ui];
-        for (int l = 0; l < a->ion_nlevels[ui]; l++) {
-          const int ul = base + l;
-          const MaMeta &m = mm[ul];
-          for (int j = 0; j < m.nd; j++) {
-            const int t = base + a->line_lowerlevelindex[a->downtrans_lineindex[m.doff + j]];
-            dt[m.doff + j] = make_int2(t, mm[t].rec_off);
-          }
-          for (int j = 0; j < m.nu; j++) {
-            const int t = base + a->line_upperlevelindex[a->uptrans_lineindex[m.uoff + j]];
-            ut[m.uoff + j] = make_int2(t, mm[t].rec_off);
-          }
-        }
-      }
-    rc |= dupload(&T.down_target, dt.data(), dt.size());
-    rc |= dupload(&T.up_target, ut.data(), ut.size());
-  }
-  G.ma_key_stride = marec;
-  G.ma_cache_ok = ma_cache_ok;
+  rc |= dupload(&T.ma_meta, ma.meta.data(), nl);
+  rc |= dupload(&T.ma_walk, ma.walk.data(), nl);
+  rc |= dupload(&T.ma_dbl_off, ma.dbl_off.data(), nl + 1);
+  rc |= dupload(&T.down_target, ma.down_target);
+  rc |= dupload(&T.up_target, ma.up_target);
+  G.h_dbl_off = ma.dbl_off;
+  G.ma_key_stride = ma.key_stride;
+  G.ma_cache_ok = ma.cache_ok;
   rc |= dupload(&T.allcont_nu_edge, a->allcont_nu_edge, nb);
   rc |= dupload(&T.allcont_probability, a->allcont_probability, nb);
   rc |= dupload(&T.allcont_element, a->allcont_element, nb);
@@ -3562,38 +3173,8 @@ int artis_gpu_init(int device, const artis_atomic_tables *a, const artis_geometr
   rc |= dupload(&T.allcont_target, a->allcont_phixstargetindex, nb);
   rc |= dupload(&T.allcont_upperlevel, a->allcont_upperlevel, nb);
   rc |= dupload(&T.allcont_phixstable, a->allcont_phixstable, nb);
-  {
-    std::vector<BfCont> bc(std::max(1, nb));
-    for (int i = 0; i < nb; i++) {
-      bc[i].nu_edge = a->allcont_nu_edge[i];
-      bc[i].nu_max = a->allcont_nu_edge[i] * a->last_phixs_nuovernuedge;  // (bf_contribution's expression)
-      bc[i].probability = a->allcont_probability[i];
-      bc[i].xs_off = a->allcont_phixstable[i] * a->nphixspoints;
-      bc[i].pad = 0;
-    }
-    rc |= dupload(&T.bfc, bc.data(), bc.size());
-    const int ne2 = (nb / 4 + 1) * 4;  // at least one padding entry
-    std::vector<double2> e2(ne2, make_double2(INFINITY, INFINITY));
-    for (int i = 0; i < nb; i++) e2[i] = make_double2(bc[i].nu_edge, bc[i].nu_max);
-    rc |= dupload(&T.bf_edge2, e2.data(), e2.size());
-  }
   rc |= dupload(&T.allcont_groundindex, a->allcont_index_in_groundphixslist, nb);
   rc |= dupload(&T.groundcont_nu_edge, a->groundcont_nu_edge, a->nbfcontinua_ground);
-  {
-    // per ground continuum, the allcont indices (ascending) of the ground-level continua that enter its
-    // groundcont_gamma_contr (rpkt.cc:1166-1171): update_estimators sums these instead of scanning all continua
-    const int nbfg = a->nbfcontinua_ground;
-    std::vector<int32_t> off(nbfg + 1, 0), lst;
-    for (int g = 0; g < nbfg; g++) {
-      off[g] = (int32_t)lst.size();
-      for (int i = 0; i < nb; i++)
-        if (a->allcont_level[i] == 0 && a->allcont_index_in_groundphixslist[i] == g) lst.push_back(i);
-    }
-    off[nbfg] = (int32_t)lst.size();
-    if (lst.empty()) lst.push_back(0);
-    rc |= dupload(&T.gc_cont_off, off.data(), off.size());
-    rc |= dupload(&T.gc_cont, lst.data(), lst.size());
-  }
   rc |= dupload(&T.groundcont_element, a->groundcont_element, a->nbfcontinua_ground);
   rc |= dupload(&T.groundcont_ion, a->groundcont_ion, a->nbfcontinua_ground);
   rc |= dupload(&T.spontrecombcoeff, a->spontrecombcoeff, (size_t)a->tablesize * nb);
@@ -3604,24 +3185,44 @@ int artis_gpu_init(int device, const artis_atomic_tables *a, const artis_geometr
   rc |= dupload(&T.cool_ion, a->coolinglist_ion, a->ncoolingterms);
   rc |= dupload(&T.cool_level, a->coolinglist_level, a->ncoolingterms);
   rc |= dupload(&T.cool_upper, a->coolinglist_upperlevel, a->ncoolingterms);
-  // photoionisation target slots -> (unique level, target index)
-  std::vector<int32_t> tul(ntg + 1), tt(ntg + 1);
-  for (int ul = 0; ul < nl; ul++)
-    for (int t = 0; t < a->level_nphixstargets[ul]; t++) {
-      tul[a->level_phixstargets_offset[ul] + t] = ul;
-      tt[a->level_phixstargets_offset[ul] + t] = t;
-    }
-  const int32_t *dtul, *dtt;
-  rc |= dupload(&dtul, tul.data(), ntg + 1);
-  rc |= dupload(&dtt, tt.data(), ntg + 1);
-  G.d_target_ul = const_cast<int32_t *>(dtul);
-  G.d_target_t = const_cast<int32_t *>(dtt);
+  {
+    const ContTables ct = derive_cont_tables(a);
+    const int32_t *dtul, *dtt, *dbc;
+    rc |= dupload(&T.bfc, ct.bfc);
+    rc |= dupload(&T.bf_edge2, ct.bf_edge2);
+    rc |= dupload(&T.gc_cont_off, ct.gc_cont_off);
+    rc |= dupload(&T.gc_cont, ct.gc_cont);
+    rc |= dupload(&T.slot_allcont, ct.slot_allcont);
+    rc |= dupload(&dtul, ct.target_ul);
+    rc |= dupload(&dtt, ct.target_t);
+    rc |= dupload(&dbc, ct.bfcol);
+    if (rc) return ARTIS_ERR_HIP;
+    G.d_target_ul = const_cast<int32_t *>(dtul);
+    G.d_target_t = const_cast<int32_t *>(dtt);
+    G.d_bfcol = const_cast<int32_t *>(dbc);
+  }
+  // the nebular options' tables
+  T.total_nlte_levels = rp->nlte_pops_on ? a->total_nlte_levels : 0;
+  T.rf_nbins = rp->multibin_radfield ? a->radfield_nbins : 0;
+  T.rf_nu_lower_first = a->radfield_nu_lower_first;
+  if (rp->nlte_pops_on) {
+    rc |= dupload(&T.ion_nlevels_nlte, a->ion_nlevels_nlte, ni);
+    rc |= dupload(&T.ion_first_nlte, a->ion_first_nlte, ni);
+  }
+  if (rp->multibin_radfield) rc |= dupload(&T.rf_nu_upper, a->radfield_nu_upper, a->radfield_nbins);
+  G.nelements = ne;
+  G.maxnions = a->maxnions;
+  G.nions_total = ni;
+  G.nlines = nli;
+  return rc ? ARTIS_ERR_HIP : 0;
+}
 
-  // geometry
+static int upload_geometry(const artis_geometry *g) {
   DevGeom &GG = G.K.G;
   for (int d = 0; d < 3; d++) GG.ncoordgrid[d] = g->ncoordgrid[d];
   GG.ngrid = g->ngrid;
   GG.npts_model = g->npts_model;
+  int rc = 0;
   rc |= dupload(&GG.cell_pos_min, g->cell_pos_min, (size_t)g->ngrid * 3);
   rc |= dupload(&GG.cell_mgi, g->cell_mgi, g->ngrid);
   GG.spherical = g->grid_type == ARTIS_GRID_SPHERICAL1D;
@@ -3633,13 +3234,19 @@ int artis_gpu_init(int device, const artis_atomic_tables *a, const artis_geometr
   GG.vmax = g->vmax;
   GG.rmax = g->rmax;
   GG.wid = 2 * g->coordmax[0] / g->ncoordgrid[0];  // grid.cc:76-91
-  G.ntstep = g->ntstep;
   rc |= dupload(&GG.ts_start, g->ts_start, g->ntstep);
   rc |= dupload(&GG.ts_width, g->ts_width, g->ntstep);
   rc |= dupload(&GG.ts_mid, g->ts_mid, g->ntstep);
   GG.nu_min_r = g->nu_min_r;
   GG.nu_max_r = g->nu_max_r;
+  G.ntstep = g->ntstep;
+  G.npts_model = g->npts_model;
+  G.ngrid = g->ngrid;
+  return rc ? ARTIS_ERR_HIP : 0;
+}
 
+static void set_run_params(const artis_run_params *rp) {
+  G.params = *rp;
   DevRun &R = G.K.R;
   R.seed = rp->seed;
   R.rank = rp->rank;
@@ -3655,10 +3262,6 @@ int artis_gpu_init(int device, const artis_atomic_tables *a, const artis_geometr
   R.gamma_grey = rp->gamma_grey;
   R.instant_particle_deposition = rp->instant_particle_deposition;
   R.nt_solve_spencerfano = rp->nt_solve_spencerfano;
-  if (rp->excitation_temperature != ARTIS_TEXC_TJ && rp->excitation_temperature != ARTIS_TEXC_TE) {
-    G.last_error = "artis_run_params.excitation_temperature must be ARTIS_TEXC_TJ or ARTIS_TEXC_TE";
-    return ARTIS_ERR_BAD_ARGUMENT;
-  }
   R.exc_te = rp->excitation_temperature == ARTIS_TEXC_TE;
   R.minpop = rp->minpop > 0. ? rp->minpop : 1e-30;
   R.nlte_on = rp->nlte_pops_on;
@@ -3678,137 +3281,54 @@ int artis_gpu_init(int device, const artis_atomic_tables *a, const artis_geometr
   R.time_syn_first = rp->time_syn_first;
   R.time_syn_last = rp->time_syn_last;
   for (int d = 0; d < 3; d++) R.syn_dir[d] = rp->syn_dir[d];
-  if (R.comp_est && (R.emiss_max < 1 || R.emiss_max > ARTIS_EMISS_MAX)) {
-    G.last_error = "artis_run_params.emiss_max must be in [1, ARTIS_EMISS_MAX] with comp_est (input.cc:1821-1824)";
-    return ARTIS_ERR_BAD_ARGUMENT;
-  }
-  if ((R.nlte_on && (!a->ion_nlevels_nlte || !a->ion_first_nlte || a->total_nlte_levels < 0)) ||
-      (R.multibin && (a->radfield_nbins <= 0 || !a->radfield_nu_upper)) || R.nt_max_auger < 0) {
-    G.last_error = "nebular run parameters without the atomic tables they need (ion_nlevels_nlte / radfield bins)";
-    return ARTIS_ERR_BAD_ARGUMENT;
-  }
-  T.total_nlte_levels = R.nlte_on ? a->total_nlte_levels : 0;
-  T.rf_nbins = R.multibin ? a->radfield_nbins : 0;
-  T.rf_nu_lower_first = a->radfield_nu_lower_first;
-  if (R.nlte_on) {
-    rc |= dupload(&T.ion_nlevels_nlte, a->ion_nlevels_nlte, ni);
-    rc |= dupload(&T.ion_first_nlte, a->ion_first_nlte, ni);
-  }
-  if (R.multibin) rc |= dupload(&T.rf_nu_upper, a->radfield_nu_upper, a->radfield_nbins);
-  {
-    // get_bfcontindex (radfield.cc:1329-1341): the allcont entry of each photoionisation target slot
-    std::vector<int32_t> sa(ntg + 1, -1);
-    for (int ib = 0; ib < nb; ib++) {
-      const int ul = a->ion_uniqueleveloffset[a->elem_uniqueionoffset[a->allcont_element[ib]] + a->allcont_ion[ib]] +
-                     a->allcont_level[ib];
-      sa[a->level_phixstargets_offset[ul] + a->allcont_phixstargetindex[ib]] = ib;
-    }
-    rc |= dupload(&T.slot_allcont, sa.data(), ntg + 1);
-    // bflist (input.cc:1153-1160: cont_index counts down from -1 over every level's targets) -> ion column
-    std::vector<int32_t> bc(std::max(nb, 1), 0);
-    for (int e = 0; e < ne; e++)
-      for (int i = 0; i < a->elem_nions[e]; i++) {
-        const int ui = a->elem_uniqueionoffset[e] + i;
-        for (int l = 0; l < a->ion_nlevels[ui]; l++) {
-          const int ul = a->ion_uniqueleveloffset[ui] + l;
-          for (int t = 0; t < a->level_nphixstargets[ul]; t++) {
-            const int bi = -1 - (a->level_cont_index[ul] - t);
-            if (bi >= 0 && bi < nb) bc[bi] = e * a->maxnions + i;
-          }
-        }
-      }
-    const int32_t *dbc;
-    rc |= dupload(&dbc, bc.data(), bc.size());
-    G.d_bfcol = const_cast<int32_t *>(dbc);
-  }
+}
 
-  // estimators: one double block [J | nuJ | ffheat | colheat | rpkt_emiss | gamma | bfheat | scalars(10) |
-  // bfrate_raw | radfield J_raw | nuJ_raw | contribcount | compton_emiss] (the nebular sections only when their
-  // option is on)
-  const int np = g->npts_model;
-  const int64_t nion_est = (int64_t)np * ne * a->maxnions;
-  G.nbf_est = R.detailed_bf ? nb : 0;
-  G.nbins_est = T.rf_nbins;
-  G.n_est_doubles = 5 * (int64_t)np + 2 * nion_est + 10 + (int64_t)np * (G.nbf_est + 3 * G.nbins_est) +
-                    ((int64_t)np + 1) * ARTIS_EMISS_MAX;
-  rc |= dalloc(&G.d_estblock, G.n_est_doubles);
+// the estimator block and the event counters
+static int lay_out_estimators_on_device(const artis_atomic_tables *a, const artis_geometry *g,
+                                        const artis_run_params *rp) {
+  const EstLayout L = lay_out_estimators(a, g, rp);
+  G.nbf_est = L.nbf_est;
+  G.nbins_est = L.nbins_est;
+  G.n_est_doubles = L.n_doubles;
+  if (dalloc(&G.d_estblock, G.n_est_doubles)) return ARTIS_ERR_HIP;
+  int rc = 0;
   DevEst &E = G.K.E;
-  E.J = G.d_estblock;
-  E.nuJ = E.J + np;
-  E.ffheat = E.nuJ + np;
-  E.colheat = E.ffheat + np;
-  E.rpkt_emiss = E.colheat + np;
-  E.gamma = E.rpkt_emiss + np;
-  E.bfheat = E.gamma + nion_est;
-  E.scalars = E.bfheat + nion_est;
-  E.bfrate = E.scalars + 10;
-  E.rfJ = E.bfrate + (int64_t)np * G.nbf_est;
-  E.rfnuJ = E.rfJ + (int64_t)np * G.nbins_est;
-  E.rfcount = E.rfnuJ + (int64_t)np * G.nbins_est;
-  E.compton = E.rfcount + (int64_t)np * G.nbins_est;
-  rc |= dalloc(&E.ecounter, nli);
-  rc |= dalloc(&E.acounter, nli);
+  E.J = G.d_estblock + L.J;
+  E.nuJ = G.d_estblock + L.nuJ;
+  E.ffheat = G.d_estblock + L.ffheat;
+  E.colheat = G.d_estblock + L.colheat;
+  E.rpkt_emiss = G.d_estblock + L.rpkt_emiss;
+  E.gamma = G.d_estblock + L.gamma;
+  E.bfheat = G.d_estblock + L.bfheat;
+  E.scalars = G.d_estblock + L.scalars;
+  E.bfrate = G.d_estblock + L.bfrate;
+  E.rfJ = G.d_estblock + L.rfJ;
+  E.rfnuJ = G.d_estblock + L.rfnuJ;
+  E.rfcount = G.d_estblock + L.rfcount;
+  E.compton = G.d_estblock + L.compton;
+  rc |= dalloc(&E.ecounter, a->nlines);
+  rc |= dalloc(&E.acounter, a->nlines);
   rc |= dalloc(&E.counters, ARTIS_COUNTER_COUNT + 1);
   rc |= dalloc(&E.work, ARTIS_WORK_COUNT);
   rc |= dalloc(&E.err, 4);
-  if (rc) return ARTIS_ERR_HIP;
-  G.npts_model = np;
-  G.nelements = ne;
-  G.maxnions = a->maxnions;
-  G.nions_total = ni;
-  G.nlines = nli;
-  G.ngrid = g->ngrid;
-  // non-empty model cells: those referenced by a propagation cell, numbered from the centre outwards (the
-  // distance of the cell's nearest propagation-cell centre at tmin, ties by mgi) -- the per-cell tables that only
-  // fit the HBM budget for some cells (line coefficients, macro-atom keys) hold the first rows, the cells where
-  // the packets start and the density peaks; every other cell takes the equivalent table-free path
-  std::vector<int32_t> ne_index(np, -1), ne_mgi;
-  std::vector<double> rmin(np, DBL_MAX);
-  for (int c = 0; c < g->ngrid; c++) {
-    const int mgi = g->cell_mgi[c];
-    if (mgi >= 0 && mgi < np) {
-      double r2 = 0.;
-      if (g->grid_type == ARTIS_GRID_SPHERICAL1D) {
-        const double r = g->cell_pos_min[3 * (int64_t)c] + 0.5 * g->modelcell_wid_init[c];  // get_cellradialpos
-        r2 = r * r;
-      } else {
-        for (int d = 0; d < 3; d++) {
-          const double x = g->cell_pos_min[3 * (int64_t)c + d] + g->coordmax[d] / std::max(1, g->ncoordgrid[d]);
-          r2 += x * x;
-        }
-      }
-      rmin[mgi] = std::min(rmin[mgi], r2);
-      ne_index[mgi] = 0;
-    }
-  }
-  for (int mgi = 0; mgi < np; mgi++)
-    if (ne_index[mgi] == 0) ne_mgi.push_back(mgi);
-  std::stable_sort(ne_mgi.begin(), ne_mgi.end(), [&](int a, int b) { return rmin[a] < rmin[b]; });
-  for (size_t k = 0; k < ne_mgi.size(); k++) ne_index[ne_mgi[k]] = (int32_t)k;
-  const int nne_cells = (int)ne_mgi.size();
-  const int32_t *dnei, *dnem;
-  rc |= dupload(&dnei, ne_index.data(), np);
-  rc |= dupload(&dnem, ne_mgi.data(), nne_cells);
+  return rc ? ARTIS_ERR_HIP : 0;
+}
+
+// the non-empty cells' numbering and the per-cell tables every mode has
+static int number_cells_on_device(const artis_atomic_tables *a, const artis_geometry *g) {
+  const CellNumbering cn = number_cells(g);
+  const int nne_cells = (int)cn.ne_mgi.size();
+  const int nl = a->nlevels_total, ni = a->nions_total, nb = a->nbfcontinua, ntg = G.K.T.ntargets_total;
   DevCells &C = G.K.C;
-  C.ne_index = dnei;
-  C.ne_mgi = dnem;
+  int rc = 0;
+  rc |= dupload(&C.ne_index, cn.ne_index.data(), g->npts_model);
+  rc |= dupload(&C.ne_mgi, cn.ne_mgi.data(), nne_cells);
   C.n_nonempty = nne_cells;
-  {
-    // few-cell models: k_rpkt accumulates the estimators of every non-empty cell per block in LDS, as many of the
-    // sections as fit (ARTIS_GPU_NO_EST_LDS=1: none)
-    const char *ne = getenv("ARTIS_GPU_NO_EST_LDS");
-    const bool allow = !(ne && ne[0] == '1');
-    int64_t off = 0;
-    auto take = [&](bool want, int64_t n) -> int32_t {
-      if (!allow || !want || n <= 0 || off + n > EST_LDS_DOUBLES) return -1;
-      const int32_t o = (int32_t)off;
-      off += n;
-      return o;
-    };
-    C.est_lds_J = take(true, 3 * (int64_t)nne_cells);
-    C.est_lds_bf = take(G.K.R.detailed_bf != 0, (int64_t)nne_cells * G.K.T.nbf);
-    C.est_lds_rf = take(G.K.R.multibin != 0, 3 * (int64_t)nne_cells * G.K.T.rf_nbins);
-  }
+  const EstLdsLayout lds = lay_out_est_lds(!G.knob.no_est_lds, nne_cells, G.K.R.detailed_bf != 0, G.K.T.nbf,
+                                           G.K.R.multibin != 0, G.K.T.rf_nbins);
+  C.est_lds_J = lds.J;
+  C.est_lds_bf = lds.bf;
+  C.est_lds_rf = lds.rf;
   rc |= dalloc(&G.W.bins, (size_t)nne_cells + 1);
   rc |= dalloc(&G.d_binoffs, (size_t)nne_cells + 1);
   rc |= dalloc(&G.W.xhead, (size_t)8);
@@ -3824,6 +3344,21 @@ int artis_gpu_init(int device, const artis_atomic_tables *a, const artis_geometr
   rc |= dalloc(&C.popsT, (size_t)nne_cells * nl);
   rc |= dalloc(&C.corrphotT, (size_t)nne_cells * (ntg + 1));
   rc |= dalloc(&C.cooling, (size_t)nne_cells * a->ncoolingterms);
+  return rc ? ARTIS_ERR_HIP : 0;
+}
+
+// Macro-atom key records.  Row mode when every non-empty cell's records fit the budget (default: half of the
+// free HBM, ARTIS_GPU_MACACHE_MAX_GB; the rest is left for the packet store): cell k's records at row k.
+// Otherwise level mode: a pool of (cell, level) records within the same budget, less the per-pair action
+// totals the walks without a record read (k_ma's cooperative jump) and the pointer / activity tables; the
+// records go to the pairs the walks used most in the previous timestep (ma_level_place).
+// ARTIS_GPU_MACACHE_ROWS=r (tests) caps the budget at r rows' worth; ARTIS_GPU_NO_MACACHE=1 leaves the pool
+// empty (every jump cooperative, exact sums).  The split never changes a result.  Not getting the rows selects
+// level mode; not getting the level-mode pool is an error.
+static int size_ma_cache(const MaTables &ma) {
+  DevCells &C = G.K.C;
+  const Knobs &kn = G.knob;
+  const int nne_cells = C.n_nonempty, nl = G.K.T.nlevels_total;
   C.ma_key_stride = G.ma_key_stride;
   C.have_macache = 0;
   C.ma_rows = 0;
@@ -3833,136 +3368,107 @@ int artis_gpu_init(int device, const artis_atomic_tables *a, const artis_geometr
   C.ma_lhist = nullptr;
   C.ma_level_mode = 0;
   C.ma_hi_only = 0;
-  {
-    // Macro-atom key records.  Row mode when every non-empty cell's records fit the budget (default: half of the
-    // free HBM, ARTIS_GPU_MACACHE_MAX_GB; the rest is left for the packet store): cell k's records at row k.
-    // Otherwise level mode: a pool of (cell, level) records within the same budget, less the per-pair action
-    // totals the walks without a record read (k_ma's cooperative jump) and the pointer / activity tables; the
-    // records go to the pairs the walks used most in the previous timestep (ma_level_place).
-    // ARTIS_GPU_MACACHE_ROWS=r (tests) caps the budget at r rows' worth; ARTIS_GPU_NO_MACACHE=1 leaves the pool
-    // empty (every jump cooperative, exact sums).  The split never changes a result.
-    size_t freeb = 0, totalb = 0;
-    (void)hipMemGetInfo(&freeb, &totalb);
-    const double row_bytes = (double)C.ma_key_stride * 2.0;
-    int64_t maxlev = 0;
-    for (int ul = 0; ul < nl; ul++) maxlev = std::max(maxlev, G.h_dbl_off[ul + 1] - G.h_dbl_off[ul]);
-    int64_t cap = ((int64_t)2 << 30) / 8;  // k_marates scratch of row mode (ARTIS_GPU_MAREC_SCRATCH_MB)
-    if (const char *sm = getenv("ARTIS_GPU_MAREC_SCRATCH_MB")) cap = (int64_t)(atof(sm) * (1 << 20) / 8);
-    const int64_t scratch = std::max<int64_t>(maxlev * MARATES_PAD(nne_cells),
-                                              std::min<int64_t>(G.h_dbl_off[nl] * MARATES_PAD(nne_cells), cap));
-    double budget = 0.5 * (double)freeb;
-    if (const char *mx = getenv("ARTIS_GPU_MACACHE_MAX_GB")) budget = atof(mx) * (double)(1ull << 30);
-    const char *mr = getenv("ARTIS_GPU_MACACHE_ROWS");
-    if (mr) budget = std::min(budget, (double)atoll(mr) * row_bytes);
-    const char *env = getenv("ARTIS_GPU_NO_MACACHE");
-    const bool none = env && env[0] == '1';
-    const bool rows_fit = !none && G.ma_cache_ok &&
-                          (double)nne_cells * row_bytes + 8.0 * (double)scratch <= budget &&
-                          (double)nne_cells * row_bytes / 128.0 < 4.0e9;
-    void *mc = nullptr, *sc = nullptr;
-    if (rows_fit && dmalloc(&mc, (size_t)((double)nne_cells * row_bytes)) == hipSuccess) {
-      G.allocs.push_back(mc);
-      if (dmalloc(&sc, (size_t)scratch * 8) == hipSuccess) {
-        G.allocs.push_back(sc);
-        C.ma_key = (uint16_t *)mc;
-        C.have_macache = 1;
-        C.ma_rows = nne_cells;
-        G.d_marec_scratch = (double *)sc;
-        G.marec_scratch_doubles = scratch;
-      }
-    }
-    if (!C.ma_rows) {
-      // level mode: per level, its record size in 128-byte lines (0: never a record -- a layout that does not fit,
-      // or more rate terms than k_ma_build stages in LDS)
-      G.h_rec_lines.assign(nl, 0);
-      G.ma_build_lds_doubles = 0;
-      const bool hi_only = ARTIS_MA_HI_ONLY;  // (k_ma's level-mode instance compiles the same choice in)
-      std::vector<MaMeta> mm(nl);
-      HIPCHK(hipMemcpy(mm.data(), G.K.T.ma_meta, nl * sizeof(MaMeta), hipMemcpyDeviceToHost));
-      for (int ul = 0; ul < nl; ul++) {
-        const int64_t next = (ul + 1 < nl) ? mm[ul + 1].rec_off : G.ma_key_stride;
-        const int64_t need = ma_build_doubles(mm[ul]);
-        if (ma_layout_ok(mm[ul].nd, mm[ul].nu) && need <= MA_BUILD_MAX_DOUBLES) {
-          const int64_t hot = ma_layout(mm[ul].nd, mm[ul].nu, mm[ul].nr, mm[ul].nt).hot;
-          G.h_rec_lines[ul] = (uint32_t)(hi_only ? (hot + 63) / 64 : (next - mm[ul].rec_off) / 64);
-          G.ma_build_lds_doubles = std::max<int64_t>(G.ma_build_lds_doubles, need);
-        }
-      }
-      const double tables = (double)nne_cells * nl * (ARTIS_MA_ACTION_COUNT * 8.0 + 8.0);
-      // (ARTIS_GPU_MACACHE_ROWS: a pool of exactly that many rows' records)
-      const double pool = none ? 128.0 : mr ? std::max(128.0, budget) : std::max(128.0, budget - tables);
-      G.ma_pool_lines = (uint64_t)std::min(pool / 128.0, 4.0e9 - 1.0);
-      if (dmalloc(&mc, (size_t)G.ma_pool_lines * 128) == hipSuccess) {
-        G.allocs.push_back(mc);
-        C.ma_key = (uint16_t *)mc;
-        C.have_macache = 1;
-        C.ma_level_mode = 1;
-        C.ma_hi_only = hi_only ? 1 : 0;
-        rc |= dalloc(&C.marates, (size_t)nne_cells * nl * ARTIS_MA_ACTION_COUNT);
-        rc |= dalloc(&G.d_ma_lptr, (size_t)nne_cells * nl);
-        rc |= dalloc(&G.d_ma_lhist, (size_t)nne_cells * nl);
-        rc |= dupload(&G.d_rec_lines, G.h_rec_lines.data(), nl);
-        std::vector<uint32_t> rl_off(nl, 0);
-        uint64_t acc = 0;
-        for (int ul = 0; ul < nl; ul++) {
-          rl_off[ul] = (uint32_t)acc;
-          acc += G.h_rec_lines[ul];
-        }
-        G.row_lines = (uint32_t)acc;
-        rc |= dupload(&G.d_rl_off, rl_off.data(), nl);
-        rc |= dalloc(&G.d_lvl_ctr, (size_t)4);
-        rc |= dalloc(&G.d_lvl_buckets, (size_t)(2 + MA_LVL_NB));
-        rc |= dalloc(&G.d_build_list, (size_t)std::max<int64_t>(1, std::min<int64_t>((int64_t)nne_cells * nl,
-                                                                                   (int64_t)G.ma_pool_lines)));
-        G.build_list_cap = std::min<int64_t>((int64_t)nne_cells * nl, (int64_t)G.ma_pool_lines);
-        C.ma_lptr = G.d_ma_lptr;
-        C.ma_lhist = G.d_ma_lhist;
-        G.ma_lhist_ready = false;
-      } else {
-        rc |= ARTIS_ERR_HIP;
-      }
-    }
+  size_t freeb = 0, totalb = 0;
+  (void)hipMemGetInfo(&freeb, &totalb);
+  const double row_bytes = (double)C.ma_key_stride * 2.0;
+  int64_t maxlev = 0;
+  for (int ul = 0; ul < nl; ul++) maxlev = std::max(maxlev, G.h_dbl_off[ul + 1] - G.h_dbl_off[ul]);
+  const int64_t cap = kn.marec_scratch_doubles;  // k_marates scratch of row mode
+  const int64_t scratch = std::max<int64_t>(maxlev * MARATES_PAD(nne_cells),
+                                            std::min<int64_t>(G.h_dbl_off[nl] * MARATES_PAD(nne_cells), cap));
+  double budget = 0.5 * (double)freeb;
+  if (kn.have_macache_max) budget = kn.macache_max_bytes;
+  if (kn.have_macache_rows) budget = std::min(budget, (double)kn.macache_rows * row_bytes);
+  const bool none = kn.no_macache;
+  const bool rows_fit = !none && G.ma_cache_ok &&
+                        (double)nne_cells * row_bytes + 8.0 * (double)scratch <= budget &&
+                        (double)nne_cells * row_bytes / 128.0 < 4.0e9;
+  void *mc = nullptr, *sc = nullptr;
+  if (rows_fit && G.mem.raw(&mc, (size_t)((double)nne_cells * row_bytes)) == hipSuccess &&
+      G.mem.raw(&sc, (size_t)scratch * 8) == hipSuccess) {
+    C.ma_key = (uint16_t *)mc;
+    C.have_macache = 1;
+    C.ma_rows = nne_cells;
+    G.d_marec_scratch = (double *)sc;
+    G.marec_scratch_doubles = scratch;
+  }
+  int rc = 0;
+  if (!C.ma_rows) {
+    const bool hi_only = ARTIS_MA_HI_ONLY;  // (k_ma's level-mode instance compiles the same choice in)
+    const MaLevelTables lv = derive_ma_level_tables(ma, hi_only);
+    G.h_rec_lines = lv.rec_lines;
+    G.ma_build_lds_doubles = lv.build_lds_doubles;
+    G.row_lines = lv.row_lines;
+    const double tables = (double)nne_cells * nl * (ARTIS_MA_ACTION_COUNT * 8.0 + 8.0);
+    // (ARTIS_GPU_MACACHE_ROWS: a pool of exactly that many rows' records)
+    const double pool = none ? 128.0 : kn.have_macache_rows ? std::max(128.0, budget) : std::max(128.0, budget - tables);
+    G.ma_pool_lines = (uint64_t)std::min(pool / 128.0, 4.0e9 - 1.0);
+    HIPCHK(G.mem.raw(&mc, (size_t)G.ma_pool_lines * 128));
+    C.ma_key = (uint16_t *)mc;
+    C.have_macache = 1;
+    C.ma_level_mode = 1;
+    C.ma_hi_only = hi_only ? 1 : 0;
+    rc |= dalloc(&C.marates, (size_t)nne_cells * nl * ARTIS_MA_ACTION_COUNT);
+    rc |= dalloc(&G.d_ma_lptr, (size_t)nne_cells * nl);
+    rc |= dalloc(&G.d_ma_lhist, (size_t)nne_cells * nl);
+    rc |= dupload(&G.d_rec_lines, lv.rec_lines.data(), nl);
+    rc |= dupload(&G.d_rl_off, lv.rl_off.data(), nl);
+    rc |= dalloc(&G.d_lvl_ctr, (size_t)4);
+    rc |= dalloc(&G.d_lvl_buckets, (size_t)(2 + MA_LVL_NB));
+    G.build_list_cap = std::min<int64_t>((int64_t)nne_cells * nl, (int64_t)G.ma_pool_lines);
+    rc |= dalloc(&G.d_build_list, (size_t)std::max<int64_t>(1, G.build_list_cap));
+    C.ma_lptr = G.d_ma_lptr;
+    C.ma_lhist = G.d_ma_lhist;
+    G.ma_lhist_ready = false;
   }
   rc |= dalloc(&G.d_ma_row, (size_t)nne_cells);
   rc |= dalloc(&G.d_ma_bin, (size_t)nne_cells);
   rc |= dalloc(&G.d_ma_bincell, (size_t)nne_cells);
+  if (rc) return ARTIS_ERR_HIP;
   C.ma_row = G.d_ma_row;
   C.ma_bin = G.d_ma_bin;
-  if (!rc) {
-    std::vector<int32_t> order(nne_cells);
-    for (int k = 0; k < nne_cells; k++) order[k] = k;  // centre outwards
-    rc |= ma_place(order);
-  }
-  // per-cell line coefficients for the r-packet line walk: rows for the first linecoef_rows cells (centre
-  // outwards) within a budget of 30% of the HBM still free (the packet store comes later; ARTIS_GPU_LINECOEF_MAX_GB
-  // overrides it), ARTIS_GPU_NO_LINECOEF=1 switches them off.  Cells past the last row gather the two populations
-  // per line themselves (the same coefficient, bit for bit).
+  std::vector<int32_t> order(nne_cells);
+  for (int k = 0; k < nne_cells; k++) order[k] = k;  // centre outwards
+  return ma_place(order);
+}
+
+// Per-cell line coefficients for the r-packet line walk: rows for the first linecoef_rows cells (centre
+// outwards) within a budget of 30% of the HBM still free (the packet store comes later; ARTIS_GPU_LINECOEF_MAX_GB
+// overrides it), ARTIS_GPU_NO_LINECOEF=1 switches them off.  Cells past the last row gather the two populations
+// per line themselves (the same coefficient, bit for bit).  Not getting the rows leaves every cell gathering.
+static int size_line_coefficients() {
+  DevCells &C = G.K.C;
+  const Knobs &kn = G.knob;
   C.linecoef = nullptr;
   C.linecoef_rows = 0;
   C.linecoef_stride = ((int64_t)G.K.T.nlines + 15) / 16 * 16;  // (whole 16-line windows: k_vpkt)
-  {
-    size_t freeb = 0, totalb = 0;
-    (void)hipMemGetInfo(&freeb, &totalb);
-    double budget = 0.3 * (double)freeb;
-    if (const char *mx = getenv("ARTIS_GPU_LINECOEF_MAX_GB")) budget = atof(mx) * (double)(1ull << 30);
-    const char *env = getenv("ARTIS_GPU_NO_LINECOEF");
-    const double row_bytes = (double)C.linecoef_stride * 8.0;
-    int rows = (int)std::min<double>((double)nne_cells, std::floor(budget / row_bytes));
-    if (const char *lr = getenv("ARTIS_GPU_LINECOEF_ROWS")) rows = std::min(rows, atoi(lr));
-    if (env && env[0] == '1') rows = 0;
-    if (rows > 0) {
-      void *lc = nullptr;
-      if (dmalloc(&lc, (size_t)rows * (size_t)row_bytes) == hipSuccess) {
-        G.allocs.push_back(lc);
-        C.linecoef = (double *)lc;
-        C.linecoef_rows = rows;
-      }
-    }
+  size_t freeb = 0, totalb = 0;
+  (void)hipMemGetInfo(&freeb, &totalb);
+  double budget = 0.3 * (double)freeb;
+  if (kn.have_linecoef_max) budget = kn.linecoef_max_bytes;
+  const double row_bytes = (double)C.linecoef_stride * 8.0;
+  int rows = (int)std::min<double>((double)C.n_nonempty, std::floor(budget / row_bytes));
+  if (kn.have_linecoef_rows) rows = std::min(rows, kn.linecoef_rows);
+  if (kn.no_linecoef) rows = 0;
+  void *lc = nullptr;
+  if (rows > 0 && G.mem.raw(&lc, (size_t)rows * (size_t)row_bytes) == hipSuccess) {
+    C.linecoef = (double *)lc;
+    C.linecoef_rows = rows;
   }
   C.linecoef_neg = nullptr;
-  rc |= dalloc(&C.linecoef_neg, (size_t)1);
-  if (C.linecoef_neg) HIPCHK(hipMemset(C.linecoef_neg, 0, sizeof(int32_t)));
-  // cell-state input buffers
+  if (dalloc(&C.linecoef_neg, (size_t)1)) return ARTIS_ERR_HIP;
+  HIPCHK(hipMemset(C.linecoef_neg, 0, sizeof(int32_t)));
+  return 0;
+}
+
+// the queue counters, the device context and the buffers artis_gpu_upload_cellstate copies into
+static int alloc_cellstate_inputs(const artis_atomic_tables *a) {
+  const DevRun &R = G.K.R;
+  const DevTab &T = G.K.T;
+  DevCells &C = G.K.C;
+  const int np = G.npts_model, ne = G.nelements, ni = G.nions_total, nb = T.nbf, nne_cells = C.n_nonempty;
+  const int64_t ntg = T.ntargets_total;
+  int rc = 0;
   rc |= dalloc(&G.W.ctr, (size_t)NQUEUES * 2);
   rc |= dalloc(&G.d_ctx, (size_t)1);
   rc |= dalloc(&G.W.stats, (size_t)48);
@@ -4000,7 +3506,12 @@ int artis_gpu_init(int device, const artis_atomic_tables *a, const artis_geometr
     rc |= dalloc(&G.qag.order, nw);
     rc |= dalloc(&G.qag.level, nw);
   }
-  if (rc) return ARTIS_ERR_HIP;
+  return rc ? ARTIS_ERR_HIP : 0;
+}
+
+static void wire_ctx() {
+  DevCells &C = G.K.C;
+  const int np = G.npts_model;
   C.nlte_pops = G.d_nltepops;
   C.rf_TR = G.d_rfTR;
   C.rf_W = G.d_rfW;
@@ -4025,8 +3536,41 @@ int artis_gpu_init(int device, const artis_atomic_tables *a, const artis_geometr
   C.totalcooling = G.d_totcool;
   C.cooling_contrib_ion = G.d_ccion;
   C.corrphotoionrenorm = G.d_renorm;
+}
+
+static int init_stages(int device, const artis_atomic_tables *a, const artis_geometry *g, const artis_run_params *rp) {
+  if (int rc = validate_init(a, g, rp)) return rc;
+  if (int rc = create_stream_and_events(device)) return rc;
+  apply_knobs();
+  const MaTables ma = derive_ma_tables(a);
+  if (int rc = upload_atomic_tables(a, rp, ma)) return rc;
+  if (int rc = upload_geometry(g)) return rc;
+  set_run_params(rp);
+  if (int rc = lay_out_estimators_on_device(a, g, rp)) return rc;
+  if (int rc = number_cells_on_device(a, g)) return rc;
+  if (int rc = size_ma_cache(ma)) return rc;
+  if (int rc = size_line_coefficients()) return rc;
+  if (int rc = alloc_cellstate_inputs(a)) return rc;
+  wire_ctx();
   G.initialised = true;
   return 0;
+}
+
+int artis_gpu_init(int device, const artis_atomic_tables *a, const artis_geometry *g, const artis_run_params *rp) {
+  if (!a || !g || !rp) return ARTIS_ERR_BAD_ARGUMENT;
+  if (const char *why = unsupported_run_param(rp)) {  // (an engine already initialised survives these two)
+    G.last_error = why;
+    return ARTIS_ERR_UNSUPPORTED;
+  }
+  artis_gpu_finalize();
+  const int rc = init_stages(device, a, g, rp);
+  if (rc) {
+    // a failed init leaves nothing behind but its message
+    const std::string why = G.last_error;
+    artis_gpu_finalize();
+    G.last_error = why;
+  }
+  return rc;
 }
 
 int artis_gpu_init_gamma(const artis_gamma_spectra *gs) {
@@ -4042,29 +3586,6 @@ int artis_gpu_init_gamma(const artis_gamma_spectra *gs) {
     nlines = std::max<int64_t>(nlines, (int64_t)gs->nuc_line_offset[k] + gs->nuc_nlines[k]);
   }
   if (nlines > 0 && (!gs->line_energy || !gs->line_probability)) return ARTIS_ERR_BAD_ARGUMENT;
-  DevTab &T = G.K.T;
-  int32_t *nl = nullptr, *off = nullptr;
-  double *en = nullptr, *eg = nullptr, *pr = nullptr;
-  int rc = 0;
-  rc |= dalloc(&nl, (size_t)nn);
-  rc |= dalloc(&off, (size_t)nn);
-  rc |= dalloc(&eg, (size_t)nn);
-  rc |= dalloc(&en, (size_t)std::max<int64_t>(nlines, 1));
-  rc |= dalloc(&pr, (size_t)std::max<int64_t>(nlines, 1));
-  if (rc) return ARTIS_ERR_HIP;
-  HIPCHK(hipMemcpy(nl, gs->nuc_nlines, sizeof(int32_t) * nn, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(off, gs->nuc_line_offset, sizeof(int32_t) * nn, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(eg, gs->nuc_endecay_gamma, sizeof(double) * nn, hipMemcpyHostToDevice));
-  if (nlines > 0) {
-    HIPCHK(hipMemcpy(en, gs->line_energy, sizeof(double) * nlines, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(pr, gs->line_probability, sizeof(double) * nlines, hipMemcpyHostToDevice));
-  }
-  T.g_nnuc = nn;
-  T.g_nlines = nl;
-  T.g_off = off;
-  T.g_endecay = eg;
-  T.g_energy = en;
-  T.g_prob = pr;
   // allnuc_gamma_line_list: every nuclide's lines sorted by energy (init_gamma_linelist, gammapkt.cc:192-211); the
   // Compton emissivity bins by get_nul over its frequencies (gammapkt.cc:720-745)
   std::vector<double> fs;
@@ -4072,13 +3593,28 @@ int artis_gpu_init_gamma(const artis_gamma_spectra *gs) {
     for (int j = 0; j < gs->nuc_nlines[k]; j++) fs.push_back(gs->line_energy[gs->nuc_line_offset[k] + j]);
   std::sort(fs.begin(), fs.end());
   for (double &f : fs) f /= ARTIS_H;
+  DevBufs B;  // the new tables: replace their predecessors (Engine::mem_gamma) once they are complete
+  const int32_t *nl = nullptr, *off = nullptr;
+  const double *en = nullptr, *eg = nullptr, *pr = nullptr, *dfs = nullptr;
+  int rc = 0;
+  rc |= dupload(B, &nl, gs->nuc_nlines, (size_t)nn);
+  rc |= dupload(B, &off, gs->nuc_line_offset, (size_t)nn);
+  rc |= dupload(B, &eg, gs->nuc_endecay_gamma, (size_t)nn);
+  rc |= dupload(B, &en, nlines > 0 ? gs->line_energy : nullptr, (size_t)std::max<int64_t>(nlines, 1));
+  rc |= dupload(B, &pr, nlines > 0 ? gs->line_probability : nullptr, (size_t)std::max<int64_t>(nlines, 1));
+  if (!fs.empty()) rc |= dupload(B, &dfs, fs.data(), fs.size());
+  if (rc) return ARTIS_ERR_HIP;
+  G.mem_gamma.release();
+  G.mem_gamma.p.swap(B.p);
+  DevTab &T = G.K.T;
+  T.g_nnuc = nn;
+  T.g_nlines = nl;
+  T.g_off = off;
+  T.g_endecay = eg;
+  T.g_energy = en;
+  T.g_prob = pr;
   T.g_nsorted = (int32_t)fs.size();
-  if (!fs.empty()) {
-    const double *dfs;
-    rc |= dupload(&dfs, fs.data(), fs.size());
-    if (rc) return ARTIS_ERR_HIP;
-    T.g_freq_sorted = dfs;
-  }
+  T.g_freq_sorted = dfs;
   return 0;
 }
 
@@ -4168,9 +3704,7 @@ int artis_gpu_upload_cellstate(int nts, const artis_cell_state *cs) {
     if (G.K.C.linecoef) HIPCHK(hipMemsetAsync(G.K.C.linecoef_neg, 0, sizeof(int32_t), G.stream));
     if (G.K.C.linecoef) {
       const int lc_rows_lds = (int)std::min<int64_t>(5, LINECOEF_LDS_DOUBLES / std::max<int64_t>(1, nl));
-      const char *lcg = getenv("ARTIS_GPU_LINECOEF_GATHER");  // (A/B and test switch: the gather kernel)
-      const bool lc_gather = lcg && atoi(lcg);
-      if (lc_rows_lds >= 1 && !lc_gather)
+      if (lc_rows_lds >= 1 && !G.knob.linecoef_gather)  // (ARTIS_GPU_LINECOEF_GATHER: the gather kernel)
         k_linecoef_lds<<<(unsigned)std::min<int64_t>((G.K.C.linecoef_rows + lc_rows_lds - 1) / lc_rows_lds,
                                                      (int64_t)G.wave_grid / 2),  // (4 blocks per CU; one fits)
                          1024, 0, G.stream>>>(G.K, lc_rows_lds);
@@ -4300,7 +3834,7 @@ int artis_gpu_update_packets_resident(int my_rank, int nts) {
   }
   HIPCHK(hipEventRecord(G.ev0, G.stream));
   G.last_rounds = 0;
-  if (n > 0 && G.use_megakernel) {
+  if (n > 0 && G.knob.use_megakernel) {
     if (int rc = sync_ctx()) return rc;
     k_transport<<<(unsigned)((n + TRANSPORT_BLOCK - 1) / TRANSPORT_BLOCK), TRANSPORT_BLOCK, 0, G.stream>>>(
         G.d_ctx, G.d_soa, n, nts, t2);
@@ -4325,7 +3859,7 @@ int artis_gpu_update_packets_resident(int my_rank, int nts) {
   unsigned long long w[ARTIS_WORK_COUNT];
   HIPCHK(hipMemcpy(w, G.K.E.work, sizeof(w), hipMemcpyDeviceToHost));
   for (int k = 0; k < ARTIS_WORK_COUNT; k++) G.last_work[k] = (int64_t)w[k];
-  if (G.K.C.ma_level_mode && n > 0 && !G.use_megakernel) {
+  if (G.K.C.ma_level_mode && n > 0 && !G.knob.use_megakernel) {
     // level mode: the last transport's jumps, and those made from a record (all but the wave's exact-sum jumps,
     // WaveState::stats[45])
     unsigned long long coop = 0;

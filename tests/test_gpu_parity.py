@@ -353,6 +353,61 @@ def test_allocation_failures_fail_cleanly(small_model, engine_factory, monkeypat
     eng.close()  # idempotent
 
 
+def test_failed_init_leaves_nothing_and_repeated_vpkt_init(monkeypatch):
+    """artis_gpu_init that fails -- an injected allocation failure at an early and at later stages, an argument
+    refused by its validation -- returns its error with a message, leaves nothing allocated (finalize right after is
+    harmless) and the next engine on the same process matches the oracle.  A second artis_gpu_vpkt_init on one engine
+    replaces the first one's parameter set: the virtual-packet result is the oracle's."""
+    import ctypes as C
+
+    from artis_amd import gpu_lib
+    from artis_amd.model import Model
+    from test_gpu_vpkt import _compare_vpkt
+
+    ERR_HIP, ERR_BAD_ARGUMENT = -2, -3  # include/artis_gpu.h
+    m = Model(ngrid_1d=4, nlevels_per_ion=10, n_ionising=4, max_lines=200, ntstep=10)
+    L = gpu_lib()
+    for limit in (4096, 65536, 1048576):
+        monkeypatch.setenv("ARTIS_GPU_FAIL_ALLOC_ABOVE", str(limit))
+        rc = L.artis_gpu_init(0, m.atomic, m.geometry, C.byref(m.params))
+        msg = L.artis_gpu_last_error().decode()
+        print(f"ARTIS_GPU_FAIL_ALLOC_ABOVE={limit}: artis_gpu_init -> {rc} ({msg!r})")
+        if limit == 4096:  # (the estimator block alone is larger)
+            assert rc == ERR_HIP and msg
+        else:
+            assert rc == 0 or (rc == ERR_HIP and msg)
+        L.artis_gpu_finalize()
+        L.artis_gpu_finalize()
+    monkeypatch.delenv("ARTIS_GPU_FAIL_ALLOC_ABOVE")
+    p = ffi.RunParams.from_buffer_copy(m.params)
+    p.excitation_temperature = 7
+    assert L.artis_gpu_init(0, m.atomic, m.geometry, C.byref(p)) == ERR_BAD_ARGUMENT
+    assert L.artis_gpu_last_error().decode()
+    nts = 5
+    eng = Engine(m)
+    try:
+        _, pg, eg, po, eo, _ = _pair(m, eng, nts, 500, seed=81)
+        parity.assert_packets_match(pg, po)
+        parity.assert_estimators_match(eg, eo)
+        # the whole run inside the vspec window
+        vc = ffi.VpktConfig(nz_obs=(0.3, -0.7, 1.0), phi_obs_deg=(10.0, 200.0, 0.0), exclude=(0.0, -1.0, -2.0, 26.0),
+                            tmin_days=0.5 * m.cfg.tmin_days, tmax_days=2.0 * m.cfg.tmax_days, vgrid=True,
+                            ny_vgrid=25, nz_vgrid=25, grid_ranges_angstrom=((3500.0, 6000.0), (6000.0, 9000.0)))
+        eng.vpkt_init(vc)
+        eng.vpkt_init(vc)
+        pk = m.init_rpackets(nts, 500, seed=82)
+        pg, po = pk.copy(), pk.copy()
+        eg = eng.update_packets(nts, pg)
+        vg = eng.vpkt_download()
+        eo, vo, _ = oracle_lib.update_packets_vpkt(m, nts, po, vc, nthreads=16)
+        parity.assert_packets_match(pg, po)
+        parity.assert_estimators_match(eg, eo)
+        _compare_vpkt(vg, vo)
+        assert vo.counters()["nvpkt"] > 0
+    finally:
+        eng.close()
+
+
 def test_estimator_block_roundtrip_and_rccl(small_model, engine_factory):
     """The device block (artis_gpu_estimator_block_to_device) equals the host pack of the downloaded estimators
     (artis_estimator_block_pack, what the gloo test reduces); a block written back (from_device) is what the next
