@@ -2761,6 +2761,135 @@ int artis_gpu_spectra(const artis_spectra_request *req, artis_spectra_out *out) 
   return 0;
 }
 
+// The direction-resolved set in one pass (k_spectra_res): slot 0 the angle average (with_average), then the bins
+// [abin_first, abin_first + abin_count); every spectrum array and lc_lum carry the leading slot dimension.
+int artis_gpu_spectra_res(const artis_spectra_res_request *req, artis_spectra_out *out) {
+  if (!G.initialised) return ARTIS_ERR_NOT_INITIALISED;
+  if (!req || !out) {
+    G.last_error = "spectra_res: NULL request or output";
+    return ARTIS_ERR_BAD_ARGUMENT;
+  }
+  if (req->nnubins <= 0 || req->nprocs <= 0 || req->abin_first < 0 || req->abin_count < 0 ||
+      req->abin_first > ARTIS_MABINS || req->abin_count > ARTIS_MABINS - req->abin_first ||
+      (req->with_average != 0 && req->with_average != 1) || (req->abin_count == 0 && !req->with_average)) {
+    G.last_error = "spectra_res: bad request (nnubins, nprocs > 0; bins [abin_first, abin_first + abin_count) within "
+                   "[0, ARTIS_MABINS]; with_average 0 or 1; no bins needs with_average)";
+    return ARTIS_ERR_BAD_ARGUMENT;
+  }
+  if ((!out->emission != !out->absorption) || (out->trueemission && !out->emission) ||
+      ((out->stokes_emission || out->stokes_absorption) && !out->emission)) {
+    G.last_error = "spectra_res: inconsistent emission / absorption / Stokes arrays";
+    return ARTIS_ERR_BAD_ARGUMENT;
+  }
+  if (!req->with_average && (out->lc_lumcmf || out->gamma_lc_lum || out->gamma_lc_lumcmf)) {
+    G.last_error = "spectra_res: lc_lumcmf and the gamma-ray light curves belong to the angle average: NULL without "
+                   "with_average";
+    return ARTIS_ERR_BAD_ARGUMENT;
+  }
+  const int nt = G.ntstep, nnb = req->nnubins;
+  const int ioncount = G.nelements * G.maxnions, proccount = 2 * ioncount + 1;
+  const size_t nslots = (size_t)req->with_average + (size_t)req->abin_count;
+  const double nu_min = G.K.G.nu_min_r, nu_max = G.K.G.nu_max_r;
+  const double dlognu = (log(nu_max) - log(nu_min)) / nnb;  // spectrum.cc:352, 491-500 (host libm)
+  std::vector<double> delta(nnb);
+  for (int nnu = 0; nnu < nnb; nnu++)
+    delta[nnu] = spec_delta_freq(nu_min, dlognu, nnu);
+  const size_t nb = (size_t)nt * nnb;
+  // device accumulators, in the order of the sections below
+  struct Sec {
+    double *host;
+    size_t n;
+  } secs[] = {{out->flux, nslots * nb},
+              {out->emission, nslots * nb * proccount},
+              {out->trueemission, nslots * nb * proccount},
+              {out->absorption, nslots * nb * ioncount},
+              {out->stokes_flux, nslots * 3 * nb},
+              {out->stokes_emission, nslots * 3 * nb * proccount},
+              {out->stokes_absorption, nslots * 3 * nb * ioncount},
+              {out->lc_lum, nslots * nt},
+              {out->lc_lumcmf, (size_t)nt},
+              {out->gamma_lc_lum, (size_t)nt},
+              {out->gamma_lc_lumcmf, (size_t)nt}};
+  constexpr int NSEC = sizeof(secs) / sizeof(secs[0]);
+  size_t total = nnb;  // delta_freq first
+  for (const Sec &x : secs)
+    if (x.host) total += x.n;
+  {
+    // all slots or none: a request that does not fit is refused before anything is allocated or binned
+    size_t freeb = 0, totalb = 0;
+    HIPCHK(hipMemGetInfo(&freeb, &totalb));
+    if (total * sizeof(double) > freeb) {
+      G.last_error = "spectra_res: out of device memory: the accumulators of " + std::to_string(nslots) +
+                     " slots need " + std::to_string(total * sizeof(double)) + " bytes, " + std::to_string(freeb) +
+                     " are free; ask for fewer direction bins per call (a smaller abin_count)";
+      return ARTIS_ERR_HIP;
+    }
+  }
+  DevBufs B;  // released on every path
+  double *d = nullptr;
+  if (int rc = B.get(&d, total, (const double *)nullptr)) {
+    (void)hipGetLastError();  // the failed allocation is reported here, not by the next launch check
+    G.last_error = "spectra_res: out of device memory: allocating " + std::to_string(total * sizeof(double)) +
+                   " bytes of accumulators failed; ask for fewer direction bins per call (a smaller abin_count)";
+    return rc;
+  }
+  double *dptr[NSEC];
+  size_t off = nnb;
+  for (int k = 0; k < NSEC; k++) {
+    dptr[k] = secs[k].host ? d + off : nullptr;
+    if (secs[k].host) off += secs[k].n;
+  }
+  if (int rc = sync_ctx()) return rc;
+  HIPCHK(hipMemsetAsync(d + nnb, 0, (total - nnb) * sizeof(double), G.stream));
+  HIPCHK(hipMemcpyAsync(d, delta.data(), nnb * sizeof(double), hipMemcpyHostToDevice, G.stream));
+  SpecArgs A{};
+  A.nnubins = nnb;
+  A.nprocs = req->nprocs;
+  A.abin = -1;
+  A.ntstep = nt;
+  A.proccount = proccount;
+  A.ioncount = ioncount;
+  A.maxnions = G.maxnions;
+  A.nbf = G.K.T.nbf;
+  for (int k = 0; k < 3; k++) A.syn_dir[k] = req->syn_dir[k];
+  A.dlognu = dlognu;
+  A.delta_freq = d;
+  A.bf_col = G.d_bfcol;
+  A.line_elem = G.K.T.line_elem;
+  A.line_ion = G.K.T.line_ion;
+  A.flux = dptr[0];
+  A.emission = dptr[1];
+  A.trueemission = dptr[2];
+  A.absorption = dptr[3];
+  A.sflux = dptr[4];
+  A.semission = dptr[5];
+  A.sabsorption = dptr[6];
+  A.lc = dptr[7];
+  A.lccmf = dptr[8];
+  A.glc = dptr[9];
+  A.glccmf = dptr[10];
+  const SpecResArgs R{req->abin_first, req->abin_count, req->with_average};
+  if (G.npkts > 0)
+    k_spectra_res<<<(unsigned)((G.npkts + 255) / 256), 256, 0, G.stream>>>(G.d_ctx, G.d_soa, G.npkts, A, R);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(G.stream));  // a kernel fault is reported before anything is added to the caller's arrays
+  // copy back through a bounded staging buffer and ADD
+  std::vector<double> h;
+  constexpr size_t STAGE = (size_t)8 << 20;  // doubles (64 MiB)
+  for (int k = 0; k < NSEC; k++) {
+    if (!secs[k].host) continue;
+    for (size_t o = 0; o < secs[k].n; o += STAGE) {
+      const size_t m = std::min(STAGE, secs[k].n - o);
+      h.resize(m);
+      HIPCHK(hipMemcpyAsync(h.data(), dptr[k] + o, m * sizeof(double), hipMemcpyDeviceToHost, G.stream));
+      HIPCHK(hipStreamSynchronize(G.stream));
+      double *dst = secs[k].host + o;
+      for (size_t j = 0; j < m; j++) dst[j] += h[j];
+    }
+  }
+  return 0;
+}
+
 int artis_gpu_vpkt_init(const artis_vpkt_params *vp) {
   if (!G.initialised) return ARTIS_ERR_NOT_INITIALISED;
   if (!vp || vp->nobs <= 0 || vp->nspectra <= 0 || vp->nspectra > ARTIS_VPKT_MAX_SPECTRA || vp->nrange < 0 ||

@@ -100,46 +100,61 @@ DEVFN int escapedirectionbin(const double dir_in[3], const double syn_dir[3]) {
   return (costhetabin * 10) + phibin;
 }
 
-__global__ void k_spectra(const Ctx *__restrict__ ctxp, const uint64_t *__restrict__ soa, int64_t n, SpecArgs A) {
-  const Ctx &K = *ctxp;
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  if (hi32(soa[PW(n, i, 0)]) != ARTIS_TYPE_ESCAPE) return;
+// One escaped packet as both exspec kernels see it: the words every contribution needs, read once.
+struct SpecPkt {
+  int escape_type, escape_time;
+  double dir[3];
+  double e_cmf, e_rf;
+  double t_arrive, cmfcorr, t_arrive_cmf;
+};
+
+// false: packet i has not escaped
+DEVFN bool spec_load(const Ctx &K, const uint64_t *__restrict__ soa, int64_t n, int64_t i, SpecPkt &P) {
+  if (hi32(soa[PW(n, i, 0)]) != ARTIS_TYPE_ESCAPE) return false;
   const uint64_t w32 = soa[PW(n, i, 32)];
-  const int escape_type = lo32(w32);
-  const int escape_time = hi32(w32);
+  P.escape_type = lo32(w32);
+  P.escape_time = hi32(w32);
   const double pos[3] = {asd(soa[PW(n, i, 3)]), asd(soa[PW(n, i, 4)]), asd(soa[PW(n, i, 5)])};
-  const double dir[3] = {asd(soa[PW(n, i, 6)]), asd(soa[PW(n, i, 7)]), asd(soa[PW(n, i, 8)])};
-  const double e_cmf = asd(soa[PW(n, i, 9)]);
-  const double e_rf = asd(soa[PW(n, i, 10)]);
+  P.dir[0] = asd(soa[PW(n, i, 6)]);
+  P.dir[1] = asd(soa[PW(n, i, 7)]);
+  P.dir[2] = asd(soa[PW(n, i, 8)]);
+  P.e_cmf = asd(soa[PW(n, i, 9)]);
+  P.e_rf = asd(soa[PW(n, i, 10)]);
+  P.t_arrive = P.escape_time - (dot(pos, P.dir) / ARTIS_CLIGHT_PROP);
+  P.cmfcorr = sqrt(1. - (K.G.vmax * K.G.vmax / ARTIS_CLIGHTSQUARED));
+  P.t_arrive_cmf = P.escape_time * P.cmfcorr;
+  return true;
+}
+
+// add_to_lc_res for the gamma-ray light curve (spectrum.cc:678-680): angle-averaged only
+DEVFN void spec_add_gamma(const Ctx &K, const SpecArgs &A, const SpecPkt &P) {
   const double tmin = K.G.tmin, tmax = K.G.tmax;
-  const double t_arrive = escape_time - (dot(pos, dir) / ARTIS_CLIGHT_PROP);
-  const double cmfcorr = sqrt(1. - (K.G.vmax * K.G.vmax / ARTIS_CLIGHTSQUARED));
-  const double t_arrive_cmf = escape_time * cmfcorr;
-  if (escape_type == ARTIS_TYPE_GAMMA) {
-    if (A.abin != -1) return;
-    // add_to_lc_res for the gamma-ray light curve (spectrum.cc:678-680)
-    if (t_arrive > tmin && t_arrive < tmax && A.glc) {
-      const int nt = spec_timestep(K, A.ntstep, t_arrive);
-      if (nt >= 0) unsafeAtomicAdd(&A.glc[nt], e_rf / K.G.ts_width[nt] / A.nprocs);
-    }
-    if (t_arrive_cmf > tmin && t_arrive_cmf < tmax && A.glccmf) {
-      const int nt = spec_timestep(K, A.ntstep, t_arrive_cmf);
-      if (nt >= 0) unsafeAtomicAdd(&A.glccmf[nt], e_cmf / K.G.ts_width[nt] / A.nprocs / cmfcorr);
-    }
-    return;
+  if (P.t_arrive > tmin && P.t_arrive < tmax && A.glc) {
+    const int nt = spec_timestep(K, A.ntstep, P.t_arrive);
+    if (nt >= 0) unsafeAtomicAdd(&A.glc[nt], P.e_rf / K.G.ts_width[nt] / A.nprocs);
   }
-  if (escape_type != ARTIS_TYPE_RPKT) return;
-  if (A.abin >= 0 && escapedirectionbin(dir, A.syn_dir) != A.abin) return;
-  const double anglefactor = (A.abin >= 0) ? ARTIS_MABINS : 1.;
-  // light_curve.cc:34-62 add_to_lc_res (the direction-bin branch has no cmf light curve)
-  if (t_arrive > tmin && t_arrive < tmax && A.lc) {
+  if (P.t_arrive_cmf > tmin && P.t_arrive_cmf < tmax && A.glccmf) {
+    const int nt = spec_timestep(K, A.ntstep, P.t_arrive_cmf);
+    if (nt >= 0) unsafeAtomicAdd(&A.glccmf[nt], P.e_cmf / K.G.ts_width[nt] / A.nprocs / P.cmfcorr);
+  }
+}
+
+// Everything one escaped r-packet adds to one output set: add_to_lc_res (light_curve.cc:34-62) and add_to_spec_res
+// (spectrum.cc:339-452) with weight anglefactor, into slot `slot` of the spectrum arrays ([slot][ntstep][nnubins]
+// [columns]; the Stokes blocks [slot][3]...) and into the light curves lc / lccmf ([ntstep], NULL: not produced --
+// a direction bin has no cmf light curve).  Shared by k_spectra (slot 0) and k_spectra_res, so the two add the same
+// numbers.  Every index is int64_t from its first product: slots * ntstep * nnubins * proccount * 3 passes 2^31.
+DEVFN void spec_add_rpkt(const Ctx &K, const uint64_t *__restrict__ soa, int64_t n, int64_t i, const SpecArgs &A,
+                         const SpecPkt &P, double anglefactor, int64_t slot, double *lc, double *lccmf) {
+  const double tmin = K.G.tmin, tmax = K.G.tmax;
+  const double t_arrive = P.t_arrive, t_arrive_cmf = P.t_arrive_cmf, e_rf = P.e_rf;
+  if (t_arrive > tmin && t_arrive < tmax && lc) {
     const int nt = spec_timestep(K, A.ntstep, t_arrive);
-    if (nt >= 0) unsafeAtomicAdd(&A.lc[nt], e_rf / K.G.ts_width[nt] * anglefactor / A.nprocs);
+    if (nt >= 0) unsafeAtomicAdd(&lc[nt], e_rf / K.G.ts_width[nt] * anglefactor / A.nprocs);
   }
-  if (A.abin == -1 && t_arrive_cmf > tmin && t_arrive_cmf < tmax && A.lccmf) {
+  if (t_arrive_cmf > tmin && t_arrive_cmf < tmax && lccmf) {
     const int nt = spec_timestep(K, A.ntstep, t_arrive_cmf);
-    if (nt >= 0) unsafeAtomicAdd(&A.lccmf[nt], e_cmf / K.G.ts_width[nt] / A.nprocs / cmfcorr);
+    if (nt >= 0) unsafeAtomicAdd(&lccmf[nt], P.e_cmf / K.G.ts_width[nt] / A.nprocs / P.cmfcorr);
   }
   // spectrum.cc:339-452 add_to_spec
   const double nu_rf = asd(soa[PW(n, i, 12)]);
@@ -153,29 +168,77 @@ __global__ void k_spectra(const Ctx *__restrict__ ctxp, const uint64_t *__restri
   const double stokes[3] = {asd(soa[PW(n, i, 25)]), asd(soa[PW(n, i, 26)]), asd(soa[PW(n, i, 27)])};
   const int64_t nb = (int64_t)A.ntstep * A.nnubins;
   const int64_t fi = (int64_t)nt * A.nnubins + nnu;
-  if (A.flux) unsafeAtomicAdd(&A.flux[fi], deltaE);
+  const int64_t pc = A.proccount, ic = A.ioncount;
+  if (A.flux) unsafeAtomicAdd(&A.flux[slot * nb + fi], deltaE);
   if (A.sflux)
-    for (int s = 0; s < 3; s++) unsafeAtomicAdd(&A.sflux[s * nb + fi], stokes[s] * deltaE);
+    for (int s = 0; s < 3; s++) unsafeAtomicAdd(&A.sflux[(slot * 3 + s) * nb + fi], stokes[s] * deltaE);
   if (!A.emission) return;
   const uint64_t w13 = soa[PW(n, i, 13)], w19 = soa[PW(n, i, 19)];
   const int nproc = spec_column(A, hi32(w13));
   const int truenproc = spec_column(A, hi32(w19));
-  const int64_t ei = fi * A.proccount;
-  unsafeAtomicAdd(&A.emission[ei + nproc], deltaE);
-  if (A.trueemission) unsafeAtomicAdd(&A.trueemission[ei + truenproc], deltaE);
+  const int64_t ei = fi * pc;
+  unsafeAtomicAdd(&A.emission[slot * nb * pc + ei + nproc], deltaE);
+  if (A.trueemission) unsafeAtomicAdd(&A.trueemission[slot * nb * pc + ei + truenproc], deltaE);
   if (A.semission)
-    for (int s = 0; s < 3; s++) unsafeAtomicAdd(&A.semission[s * nb * A.proccount + ei + nproc], stokes[s] * deltaE);
+    for (int s = 0; s < 3; s++)
+      unsafeAtomicAdd(&A.semission[(slot * 3 + s) * nb * pc + ei + nproc], stokes[s] * deltaE);
   const double absorptionfreq = asd(soa[PW(n, i, 21)]);
   const int nnu_abs = (int)((log(absorptionfreq) - log(nu_min)) / A.dlognu);
   const int at = lo32(w19);
   if (nnu_abs >= 0 && nnu_abs < A.nnubins && at >= 0 && A.absorption) {
     const double deltaE_absorption = e_rf / K.G.ts_width[nt] / A.delta_freq[nnu_abs] / 4.e12 / ARTIS_PI /
                                      ARTIS_PARSEC / ARTIS_PARSEC / A.nprocs * anglefactor;
-    const int64_t ai = ((int64_t)nt * A.nnubins + nnu_abs) * A.ioncount + A.line_elem[at] * A.maxnions + A.line_ion[at];
-    unsafeAtomicAdd(&A.absorption[ai], deltaE_absorption);
+    const int64_t ai = ((int64_t)nt * A.nnubins + nnu_abs) * ic + A.line_elem[at] * A.maxnions + A.line_ion[at];
+    unsafeAtomicAdd(&A.absorption[slot * nb * ic + ai], deltaE_absorption);
     if (A.sabsorption)
       for (int s = 0; s < 3; s++)
-        unsafeAtomicAdd(&A.sabsorption[s * nb * A.ioncount + ai], stokes[s] * deltaE_absorption);
+        unsafeAtomicAdd(&A.sabsorption[(slot * 3 + s) * nb * ic + ai], stokes[s] * deltaE_absorption);
+  }
+}
+
+__global__ void k_spectra(const Ctx *__restrict__ ctxp, const uint64_t *__restrict__ soa, int64_t n, SpecArgs A) {
+  const Ctx &K = *ctxp;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  SpecPkt P;
+  if (!spec_load(K, soa, n, i, P)) return;
+  if (P.escape_type == ARTIS_TYPE_GAMMA) {
+    if (A.abin == -1) spec_add_gamma(K, A, P);
+    return;
+  }
+  if (P.escape_type != ARTIS_TYPE_RPKT) return;
+  if (A.abin >= 0 && escapedirectionbin(P.dir, A.syn_dir) != A.abin) return;
+  const double anglefactor = (A.abin >= 0) ? ARTIS_MABINS : 1.;
+  spec_add_rpkt(K, soa, n, i, A, P, anglefactor, 0, A.lc, (A.abin == -1) ? A.lccmf : nullptr);
+}
+
+// ---- one pass for the direction-resolved set (exspec.cc:140-263: a = -1 .. MABINS-1) ---------------------------
+// Slot 0 is the angle average when with_average is set; the bins [abin_first, abin_first + abin_count) follow.  An
+// escaped r-packet belongs to the average (weight 1) and to the slot of its own direction bin (weight ARTIS_MABINS);
+// lc_lumcmf and the gamma-ray light curves exist for the average only.  Everything is a global float64 atomic, the
+// light curves included: a per-block LDS copy of them measured no faster.
+struct SpecResArgs {
+  int abin_first, abin_count, with_average;
+};
+
+__global__ void k_spectra_res(const Ctx *__restrict__ ctxp, const uint64_t *__restrict__ soa, int64_t n, SpecArgs A,
+                              SpecResArgs R) {
+  const Ctx &K = *ctxp;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  SpecPkt P;
+  if (!spec_load(K, soa, n, i, P)) return;
+  if (P.escape_type == ARTIS_TYPE_GAMMA) {
+    if (R.with_average) spec_add_gamma(K, A, P);
+    return;
+  }
+  if (P.escape_type != ARTIS_TYPE_RPKT) return;
+  const int b = escapedirectionbin(P.dir, A.syn_dir);
+  if (R.with_average) spec_add_rpkt(K, soa, n, i, A, P, 1., 0, A.lc, A.lccmf);
+  // a direction outside every bin (b < 0 or b >= ARTIS_MABINS) belongs to no slot, as in k_spectra
+  if (b >= R.abin_first && b < R.abin_first + R.abin_count) {
+    const int64_t slot = R.with_average + (b - R.abin_first);
+    spec_add_rpkt(K, soa, n, i, A, P, ARTIS_MABINS, slot, A.lc ? A.lc + slot * A.ntstep : nullptr, nullptr);
   }
 }
 

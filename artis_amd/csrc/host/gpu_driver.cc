@@ -13,6 +13,15 @@
 // ARTIS_DRIVER_TE=1: after the last timestep, update_grid's estimator preparation and temperature / ionisation
 // solution on the GPU (PacketEngine::prepare_temperatures + solve_temperatures) from that timestep's own raw
 // estimators; inputs and outputs go to <outdir>/te_case.bin for the oracle replay in tests/test_host_driver.py.
+// ARTIS_DRIVER_EXSPEC=<dir>: after the last timestep, the output directory of the reference's exspec program
+// (exspec.cc:140-263) for the packets as they then are, binned on the GPU in one pass per chunk of direction bins
+// (PacketEngine::spectra_res): light_curve.out, gamma_light_curve.out, spec.out, emission.out, emissiontrue.out,
+// absorption.out, specpol.out, emissionpol.out, absorptionpol.out, gamma_spec.out and their _res_00 .. _res_99
+// forms (do_emission_res and POL_ON; observer direction syn_dir = z).  ARTIS_DRIVER_EXSPEC_NNUBINS=<n> replaces
+// the reference's 1000 frequency bins (MNUBINS), for small test runs.
+#include <sys/stat.h>
+
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -134,6 +143,95 @@ void te_setup(const artis_atomic_tables &at, const artis_geometry &g, const arti
   c.par.accuracy = 1e-2;  // TEMPERATURE_SOLVER_ACCURACY (artisoptions_classic.h:199)
   c.par.initial_iteration = 0;
 }
+// exspec (exspec.cc:140-263) for the packets the last update left on the device: the angle-averaged files and,
+// unless the model was read as 1D shells, the 100 direction-bin sets, with do_emission_res and POL_ON.  The bins are
+// taken in chunks of at most 256 MiB of host arrays, one PacketEngine::spectra_res pass each.
+void write_exspec(artis_amd::PacketEngine &engine, const std::string &dir, const artis_atomic_tables &at,
+                  const artis_geometry &g, bool model_1d, int nnubins, const double syn_dir[3],
+                  const std::vector<double> &gamma_dep, const std::vector<double> &cmf_lum) {
+  mkdir(dir.c_str(), 0777);  // an existing directory is fine; a failure shows at the first file
+  const int nt = g.ntstep, ioncount = at.nelements * at.maxnions, proccount = 2 * ioncount + 1;
+  const size_t nb = (size_t)nt * nnubins;
+  const size_t per_slot = nb * (1 + 2 * (size_t)proccount + ioncount) + 3 * nb * (1 + (size_t)proccount + ioncount) + nt;
+  const int amax = model_1d ? 0 : ARTIS_MABINS;
+  const int cap = (int)std::max<size_t>(1, ((size_t)256 << 20) / (per_slot * sizeof(double)));
+  const std::vector<double> zeros(nb, 0.);
+  auto name = [&](const char *stem, int a) {
+    char buf[64];
+    if (a < 0)
+      std::snprintf(buf, sizeof buf, "%s.out", stem);
+    else
+      std::snprintf(buf, sizeof buf, "%s_res_%.2d.out", stem, a);
+    return dir + "/" + buf;
+  };
+  bool average_done = false;
+  for (int first = 0; !average_done || first < amax;) {
+    const int with_average = average_done ? 0 : 1;
+    const int count = std::min(cap - with_average, amax - first);
+    const size_t ns = (size_t)with_average + count;
+    std::vector<double> flux(ns * nb), em(ns * nb * proccount), tem(ns * nb * proccount), ab(ns * nb * ioncount),
+        sflux(ns * 3 * nb), sem(ns * 3 * nb * proccount), sab(ns * 3 * nb * ioncount), lc(ns * nt), lccmf(nt), glc(nt),
+        glccmf(nt);
+    artis_spectra_res_request req{};
+    req.nnubins = nnubins;
+    req.nprocs = 1;
+    req.abin_first = first;
+    req.abin_count = count;
+    req.with_average = with_average;
+    for (int k = 0; k < 3; k++) req.syn_dir[k] = syn_dir[k];
+    artis_spectra_out out{};
+    out.flux = flux.data();
+    out.emission = em.data();
+    out.trueemission = tem.data();
+    out.absorption = ab.data();
+    out.stokes_flux = sflux.data();
+    out.stokes_emission = sem.data();
+    out.stokes_absorption = sab.data();
+    out.lc_lum = lc.data();
+    if (with_average) {
+      out.lc_lumcmf = lccmf.data();
+      out.gamma_lc_lum = glc.data();
+      out.gamma_lc_lumcmf = glccmf.data();
+    }
+    engine.spectra_res(req, out);
+    for (size_t s = 0; s < ns; s++) {
+      const int a = (with_average && s == 0) ? -1 : first + (int)s - with_average;
+      if (a == -1) {
+        artis_amd::check(artis_write_light_curve(name("light_curve", a).c_str(), -1, nt, g.ts_mid, g.ts_width,
+                                                 lc.data(), lccmf.data(), gamma_dep.data(), cmf_lum.data()),
+                         "write_light_curve");
+        artis_amd::check(artis_write_light_curve(name("gamma_light_curve", a).c_str(), -1, nt, g.ts_mid, g.ts_width,
+                                                 glc.data(), glccmf.data(), gamma_dep.data(), cmf_lum.data()),
+                         "write_light_curve");
+        // no gamma packet passes add_to_spec's r-packet band test (spectrum.cc:349-350): zero flux over the gamma
+        // band's bins (exspec.cc:158-160, 214)
+        artis_amd::check(artis_write_spectrum(name("gamma_spec", a).c_str(), nullptr, nullptr, nullptr, nt, nt, g.ts_mid,
+                                              nnubins, 0.05 * 1.6021772e-6 / 6.6260755e-27,
+                                              4. * 1.6021772e-6 / 6.6260755e-27, 0, 0, zeros.data(), nullptr, nullptr,
+                                              nullptr),
+                         "write_spectrum");
+      } else {
+        artis_amd::check(artis_write_light_curve(name("light_curve", a).c_str(), a, nt, g.ts_mid, g.ts_width,
+                                                 lc.data() + s * nt, zeros.data(), nullptr, nullptr),
+                         "write_light_curve");
+      }
+      artis_amd::check(
+          artis_write_spectrum(name("spec", a).c_str(), name("emission", a).c_str(), name("emissiontrue", a).c_str(),
+                               name("absorption", a).c_str(), nt, nt, g.ts_mid, nnubins, g.nu_min_r, g.nu_max_r,
+                               proccount, ioncount, flux.data() + s * nb, em.data() + s * nb * proccount,
+                               tem.data() + s * nb * proccount, ab.data() + s * nb * ioncount),
+          "write_spectrum");
+      artis_amd::check(
+          artis_write_specpol(name("specpol", a).c_str(), name("emissionpol", a).c_str(),
+                              name("absorptionpol", a).c_str(), nt, g.ts_mid, nnubins, g.nu_min_r, g.nu_max_r, proccount,
+                              ioncount, sflux.data() + s * 3 * nb, sem.data() + s * 3 * nb * proccount,
+                              sab.data() + s * 3 * nb * ioncount),
+          "write_specpol");
+    }
+    average_done = true;
+    first += count;
+  }
+}
 template <typename T>
 void put(std::ofstream &o, const std::vector<T> &v) {
   const int64_t n = (int64_t)v.size();
@@ -205,6 +303,7 @@ int main(int argc, char **argv) {
       engine.comm_init(0, 1, id);
     }
     int last_nts = -1;
+    std::vector<double> ts_gamma_dep(cfg.ntstep, 0.), ts_cmf_lum(cfg.ntstep, 0.);  // time_step[].gamma_dep / cmf_lum
     for (int nts = nts0; nts < nts0 + nsteps && nts < cfg.ntstep; nts++) {
       last_nts = nts;
       artis_amd::check(artis_model_set_timestep(m, nts), "update_grid stand-in");
@@ -228,6 +327,8 @@ int main(int argc, char **argv) {
         engine.update_packets_reduced(rp.rank, nts, packets.data(), npkts, est);
       else
         engine.update_packets(rp.rank, nts, packets.data(), npkts, est);
+      ts_gamma_dep[nts] = est.gamma_dep;
+      ts_cmf_lum[nts] = est.cmf_lum;
       double jsum = 0.;
       for (double v : J) jsum += v;
       artis_amd::check(artis_write_temp_packetsfile(outdir.c_str(), nts, rp.rank, packets.data(), npkts),
@@ -235,6 +336,15 @@ int main(int argc, char **argv) {
       std::printf("nts %d nesc %lld cmf_lum %.17g gamma_dep %.17g pellet_decays %lld Jsum %.17g transport_ms %.3f\n",
                   nts, (long long)est.nesc, est.cmf_lum, est.gamma_dep, (long long)est.pellet_decays, jsum,
                   engine.last_transport_ms());
+    }
+    const char *exs = std::getenv("ARTIS_DRIVER_EXSPEC");
+    if (exs && exs[0] && last_nts >= 0) {
+      const char *nb = std::getenv("ARTIS_DRIVER_EXSPEC_NNUBINS");
+      const int nnubins = (nb && std::atoi(nb) > 0) ? std::atoi(nb) : 1000;
+      const double syn_dir[3] = {0., 0., 1.};
+      write_exspec(engine, exs, at, *artis_model_geometry(m), cfg.nshells_1d > 0, nnubins, syn_dir, ts_gamma_dep,
+                   ts_cmf_lum);
+      std::printf("exspec written to %s\n", exs);
     }
     const char *tev = std::getenv("ARTIS_DRIVER_TE");
     if (tev && tev[0] == '1' && last_nts >= 0 && last_nts + 1 >= cfg.ntstep) {

@@ -69,6 +69,10 @@ void PacketEngine::update_packets_reduced(int my_rank, int nts, artis_packet *pa
   check(artis_gpu_estimators_download(&est), "artis_gpu_estimators_download");
 }
 
+void PacketEngine::spectra_res(const artis_spectra_res_request &request, artis_spectra_out &out) {
+  check(artis_gpu_spectra_res(&request, &out), "artis_gpu_spectra_res");
+}
+
 double PacketEngine::last_transport_ms() const { return artis_gpu_last_transport_ms(); }
 
 }  // namespace artis_amd

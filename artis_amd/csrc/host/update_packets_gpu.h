@@ -55,6 +55,11 @@ class PacketEngine {
   // solve_Te_nltepops, nltepop.cc, nonthermal.cc's Spencer-Fano solution), cells in place
   void update_grid_nlte(const artis_nt_shells *shells, const artis_nlte_params &params, artis_nlte_cells &cells);
 
+  // exspec's binning of the packets the last update left resident (exspec.cc:140-263), all direction bins of the
+  // request in one pass (artis_gpu_spectra_res): results are ADDED into out's arrays, which carry the leading slot
+  // dimension.  Aborts like every other call here, also when the device accumulators do not fit: ask for fewer bins.
+  void spectra_res(const artis_spectra_res_request &request, artis_spectra_out &out);
+
   double last_transport_ms() const;
 };
 

@@ -445,6 +445,98 @@ def spectra_request(nnubins=1000, nprocs=1, abin=-1, syn_dir=(0., 0., 1.)):
     return r
 
 
+class SpectraResRequest(C.Structure):
+    _fields_ = [("nnubins", C.c_int32), ("nprocs", C.c_int32), ("abin_first", C.c_int32), ("abin_count", C.c_int32),
+                ("with_average", C.c_int32), ("syn_dir", C.c_double * 3)]
+
+
+class _SlotView:
+    """One slot of a SpectraResArrays, shaped like a SpectraArrays; every array is a view of the parent's block."""
+
+    def arrays(self):
+        return {n: getattr(self, n) for n, _ in SpectraOut._fields_ if getattr(self, n) is not None}
+
+
+class SpectraResArrays:
+    """Host storage of the artis_spectra_out of one artis_gpu_spectra_res call: the arrays of SpectraArrays with a
+    leading slot axis on every spectrum array and on lc_lum (slot 0 the angle average when with_average is set, then
+    the direction bins abin_first .. abin_first + abin_count - 1); lc_lumcmf and gamma_lc_* stay [ntstep] and exist
+    only with the average."""
+
+    def __init__(self, ntstep, nnubins, nelements, maxnions, abin_first=0, abin_count=MABINS, with_average=True,
+                 emission_res=True, stokes=False):
+        if not (0 <= abin_first <= MABINS and 0 <= abin_count <= MABINS - abin_first):
+            raise ValueError(f"direction bins [{abin_first}, {abin_first + abin_count}) outside [0, {MABINS}]")
+        if abin_count == 0 and not with_average:
+            raise ValueError("no slots: abin_count == 0 without with_average")
+        self.ioncount = nelements * maxnions
+        self.proccount = 2 * self.ioncount + 1
+        self.ntstep, self.nnubins = ntstep, nnubins
+        self.abin_first, self.abin_count, self.with_average = int(abin_first), int(abin_count), bool(with_average)
+        self.emission_res, self.stokes = bool(emission_res), bool(stokes)
+        ns = self.nslots = int(self.with_average) + self.abin_count
+        z = np.zeros
+        self.flux = z((ns, ntstep, nnubins))
+        self.emission = z((ns, ntstep, nnubins, self.proccount)) if emission_res else None
+        self.trueemission = z((ns, ntstep, nnubins, self.proccount)) if emission_res else None
+        self.absorption = z((ns, ntstep, nnubins, self.ioncount)) if emission_res else None
+        self.stokes_flux = z((ns, 3, ntstep, nnubins)) if stokes else None
+        self.stokes_emission = z((ns, 3, ntstep, nnubins, self.proccount)) if stokes and emission_res else None
+        self.stokes_absorption = z((ns, 3, ntstep, nnubins, self.ioncount)) if stokes and emission_res else None
+        self.lc_lum = z((ns, ntstep))
+        self.lc_lumcmf = z(ntstep) if with_average else None
+        self.gamma_lc_lum = z(ntstep) if with_average else None
+        self.gamma_lc_lumcmf = z(ntstep) if with_average else None
+        self.struct = SpectraOut()
+        for name, _ in SpectraOut._fields_:
+            a = getattr(self, name)
+            if a is not None:
+                setattr(self.struct, name, a.ctypes.data_as(C.POINTER(C.c_double)))
+
+    SLOTTED = ("flux", "emission", "trueemission", "absorption", "stokes_flux", "stokes_emission",
+               "stokes_absorption", "lc_lum")
+
+    def arrays(self):
+        return {n: getattr(self, n) for n, _ in SpectraOut._fields_ if getattr(self, n) is not None}
+
+    def abins(self):
+        """The abin of every slot, in slot order (-1: the angle average)."""
+        return ([-1] if self.with_average else []) + list(range(self.abin_first, self.abin_first + self.abin_count))
+
+    def slot_index(self, abin):
+        if abin == -1:
+            if not self.with_average:
+                raise KeyError("no angle-averaged slot (with_average is off)")
+            return 0
+        if not self.abin_first <= abin < self.abin_first + self.abin_count:
+            raise KeyError(f"direction bin {abin} outside [{self.abin_first}, {self.abin_first + self.abin_count})")
+        return int(self.with_average) + abin - self.abin_first
+
+    def slot(self, abin):
+        """Views (no copies) of slot `abin`'s arrays, shaped like a SpectraArrays.  lc_lumcmf and the gamma-ray light
+        curves belong to the average: a direction bin's view has lc_lumcmf None (light_curve.cc:56-62) and no gamma
+        curves."""
+        k = self.slot_index(abin)
+        v = _SlotView()
+        v.ioncount, v.proccount, v.nnubins, v.abin = self.ioncount, self.proccount, self.nnubins, abin
+        for name in self.SLOTTED:
+            a = getattr(self, name)
+            setattr(v, name, None if a is None else a[k])
+        for name in ("lc_lumcmf", "gamma_lc_lum", "gamma_lc_lumcmf"):
+            setattr(v, name, getattr(self, name) if abin == -1 else None)
+        return v
+
+
+def spectra_res_request(nnubins=1000, nprocs=1, abin_first=0, abin_count=MABINS, with_average=True,
+                        syn_dir=(0., 0., 1.)):
+    r = SpectraResRequest()
+    r.nnubins, r.nprocs, r.abin_first, r.abin_count = nnubins, nprocs, abin_first, abin_count
+    r.with_average = int(bool(with_average))
+    for k in range(3):
+        r.syn_dir[k] = syn_dir[k]
+    return r
+
+
 # update_grid's temperature / ionisation solution (include/artis_gpu.h artis_te_*; ABI 7)
 TE_NRATES = 8
 TE_RATE_NAMES = ["cooling_collisional", "cooling_fb", "cooling_ff", "cooling_adiabatic", "heating_collisional",

@@ -103,6 +103,13 @@ class Model:
         (self.nelements, self.maxnions, self.nions_total, self.nlevels_total, self.nlines,
          self.nbfcontinua, self.nbfcontinua_ground, self.ncoolingterms) = list(hdr)
         self.nts = 0
+        # grid::get_model_type: 1 RHO_1D_READ (shells mapped onto the grid), 3 RHO_3D_READ
+        if files is not None:
+            from . import io as aio
+
+            self.model_type = int(aio.read_input_file(files[0]).model_type)
+        else:
+            self.model_type = 1 if self.cfg.nshells_1d > 0 else 3
         self._load_gamma_lines()
         self.gamma_spectra = self._lib.artis_model_gamma_spectra(self._h)
 

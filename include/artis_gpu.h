@@ -540,6 +540,29 @@ typedef struct artis_spectra_out {
 } artis_spectra_out;
 int artis_gpu_spectra(const artis_spectra_request *req, artis_spectra_out *out);
 
+/* The direction-resolved set of exspec (exspec.cc:140-263, a = -1 .. MABINS-1) in one pass over the resident
+ * packets: an escaped r-packet is added to the angle average (weight 1) and to its own direction bin (weight
+ * ARTIS_MABINS), exactly what artis_gpu_spectra adds for abin -1 and for that abin.  `out` is the struct above with
+ * a leading slot dimension on every spectrum array and on lc_lum ([slot][ntstep][nnubins][columns], the Stokes
+ * blocks [slot][3][ntstep][nnubins][columns], lc_lum [slot][ntstep]): slot 0 is the average when with_average is
+ * set, the bins abin_first .. abin_first + abin_count - 1 follow in order.  lc_lumcmf and gamma_lc_* stay [ntstep]
+ * (light_curve.cc:56-62: a direction bin has no cmf light curve; the gamma-ray curves are angle-averaged only): they
+ * are filled with the average and must be NULL without with_average.  Results are ADDED, so the rank loop of
+ * exspec.cc:162 is one call per rank's packets with nprocs = the rank count.
+ * ARTIS_ERR_BAD_ARGUMENT (artis_gpu_last_error says why; nothing is launched, the arrays are untouched): a NULL
+ * request or output, a bin range outside [0, ARTIS_MABINS], no bins without with_average, the emission /
+ * absorption / Stokes inconsistencies artis_gpu_spectra refuses, lc_lumcmf or gamma_lc_* without with_average.
+ * The device accumulators (the size of the arrays given) are allocated per call: when they do not fit in the free
+ * device memory the call returns ARTIS_ERR_HIP before binning anything, artis_gpu_last_error states the bytes and
+ * suggests a smaller abin_count; there is no partial result. */
+typedef struct artis_spectra_res_request {
+  int32_t nnubins, nprocs;
+  int32_t abin_first, abin_count;   /* bins [abin_first, abin_first + abin_count), 0 <= .. <= ARTIS_MABINS */
+  int32_t with_average;             /* 1: slot 0 is abin -1, the bins follow; 0: bins only */
+  double syn_dir[3];
+} artis_spectra_res_request;
+int artis_gpu_spectra_res(const artis_spectra_res_request *req, artis_spectra_out *out);
+
 /* --- virtual packets (VPKT_ON) ------------------------------------------------------------------------------ */
 /* Switch virtual packets on for all following updates (replaces read_parameterfile_vpkt + init_vspecpol +
  * init_vpkt_grid, vpkt.cc:408-443, 547-578, 667-835): allocates and zeroes the device accumulators.  exclude[] > 0
@@ -773,7 +796,9 @@ double artis_gpu_last_nlte_ms(void);  /* device time (ms) of the last artis_gpu_
                                    10: Compton / pair-production emissivity estimators (artis_run_params.comp_est,
                                        artis_estimators.compton_emiss, a section of the estimator block);
                                    11: artis_gpu_init refuses unsupported option values; rlc_emiss_rpkt into
-                                       rpkt_emiss for do_rlc_est 1 / 2; artis_gpu_table_info's level-mode entries */
+                                       rpkt_emiss for do_rlc_est 1 / 2; artis_gpu_table_info's level-mode entries;
+                                       (still 11, an appended entry point breaks no caller) artis_gpu_spectra_res
+                                       and artis_spectra_res_request */
 int artis_gpu_abi_version(void);
 
 #ifdef __cplusplus
