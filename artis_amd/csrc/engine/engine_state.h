@@ -1,6 +1,7 @@
 // engine_state.h -- the host state of the engine: environment knobs, the owners of device memory, the Engine
-// singleton and HIPCHK.  Host code only; included once by engine.hip, after its kernels (Ctx, WaveState, QagWs and
-// the MA_BUILD_SMALL / VPKT_OCC_DEFAULT constants come from there).
+// singleton, HIPCHK and the call-scoped DevBufs / CallerArrays.  Host code only; included once by engine.hip, after
+// its kernels (Ctx, WaveState, QagWs and the MA_BUILD_SMALL / VPKT_OCC_DEFAULT constants come from there) and before
+// host_tables.h, nlte_tables.h and update_grid_host.h.
 #pragma once
 
 namespace {
@@ -351,6 +352,35 @@ struct DevBufs : Arena {
   int get(T **d, size_t count, const T *src) {
     if (dalloc(*this, d, count)) return ARTIS_ERR_HIP;
     if (src) HIPCHK(hipMemcpy(*d, src, count * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+  }
+};
+
+// The caller's arrays of one entry point, each listed once with its device slot, element count and host pointer:
+// allocated in B and uploaded (a NULL host pointer only allocates, which also serves for scratch), and -- io() with
+// a host pointer and a non-zero count -- noted for download(), which copies every noted array back with the size of
+// its listing.  A failed listing shows in rc.
+struct CallerArrays {
+  struct Back {
+    const void *dev;
+    void *host;
+    size_t bytes;
+  };
+  DevBufs &B;
+  std::vector<Back> back;
+  int rc = 0;
+  explicit CallerArrays(DevBufs &b) : B(b) {}
+  template <typename T>
+  void in(const T **d, size_t count, const T *host) {
+    rc |= B.get((T **)d, count, host);
+  }
+  template <typename T>
+  void io(T **d, size_t count, T *host) {
+    rc |= B.get(d, count, (const T *)host);
+    if (host && count) back.push_back({*d, host, count * sizeof(T)});
+  }
+  int download() const {
+    for (const Back &b : back) HIPCHK(hipMemcpy(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost));
     return 0;
   }
 };

@@ -1,7 +1,8 @@
 // host_tables.h -- the tables artis_gpu_init derives from the caller's atomic data and geometry before it uploads
 // them.  Pure host functions: no HIP call, no engine state.  Their expressions are the reference's, operand for
 // operand (host libm): the parity tests compare bit-level results that depend on them.  Included once by
-// engine.hip, after its kernels (ma_build_doubles and MA_BUILD_MAX_DOUBLES come from there).
+// engine.hip, after its kernels (ma_build_doubles and MA_BUILD_MAX_DOUBLES come from there) and engine_state.h;
+// nlte_tables.h holds the tables of update_grid's host drivers (update_grid_host.h).
 #pragma once
 
 namespace {

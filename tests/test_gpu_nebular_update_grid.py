@@ -9,6 +9,7 @@ the same model).  Integer outputs (pass counts, solved-timestep marks, the -1 "n
 identical; floating-point outputs agree to NEB_RTOL -- the two sides differ only by last-bit differences of the
 device libm, amplified by the iterative solves (Brent, LU refinement), which is what this tolerance bounds.
 """
+import functools
 import os
 
 import numpy as np
@@ -16,7 +17,7 @@ import pytest
 
 import oracle_lib
 import parity
-from artis_amd import Engine, ffi
+from artis_amd import Engine, EngineError, ffi
 from artis_amd.model import Model
 
 pytestmark = pytest.mark.gpu
@@ -240,10 +241,10 @@ def test_update_grid_nlte_onezone(first_rf):
     _compare_physical(m, ao, ag, cells, te_rtol=1e-3, agg_tol=2e-2)
 
 
-def test_update_grid_nlte_multicell_lte_branch():
-    """A 6-shell synthetic nebular model: every non-empty cell at once, a third of them thick (the LTE branch of
-    update_grid_cell, T_e = T_J and LTE ionisation) and a non-thermal skip timestep (nts < NUM_LTE_TIMESTEPS + 1:
-    the Spencer-Fano defaults)."""
+@functools.lru_cache(maxsize=None)
+def _multicell_case():
+    """The 6-shell synthetic nebular model with a GPU transport step's estimators, a third of the cells thick, at a
+    non-thermal skip timestep; shared by the tests below (each solves a copy of arr)."""
     m = Model(**NEB)
     nts = 5
     p = ffi.RunParams.from_buffer_copy(m.params)
@@ -252,10 +253,48 @@ def test_update_grid_nlte_multicell_lte_branch():
     nt = ffi.NtDataHandle(m)
     arr = ffi.NlteArrays(m, nts, est=est, seed=11, thick_frac=0.35)
     arr.params.num_lte_timesteps = 8
+    return m, p, nt, arr
+
+
+def test_update_grid_nlte_multicell_lte_branch():
+    """A 6-shell synthetic nebular model: every non-empty cell at once, a third of them thick (the LTE branch of
+    update_grid_cell, T_e = T_J and LTE ionisation) and a non-thermal skip timestep (nts < NUM_LTE_TIMESTEPS + 1:
+    the Spencer-Fano defaults)."""
+    m, p, nt, arr = _multicell_case()
     ao, ag, ms = _solve_both(m, p, arr, nt)
     cells = arr.mgi_list
     print(f"multicell: gpu {ms:.1f} ms for {len(cells)} cells, passes {ag.iters[cells]}")
     assert (ao.iters[cells][arr.thick[cells] == 1] == 0).all()
+    _compare_physical(m, ao, ag, cells, te_rtol=1e-3, agg_tol=2e-2)
+
+
+def _ndarrays(arr):
+    return {k: v for k, v in arr.__dict__.items() if isinstance(v, np.ndarray)}
+
+
+def test_update_grid_nlte_refused_allocation_writes_nothing(monkeypatch):
+    """A call-scoped device allocation refused in mid-call (ARTIS_GPU_FAIL_ALLOC_ABOVE, read at every allocation,
+    set below the Spencer-Fano matrix block of 8 sfpts^2 bytes per batched cell and above the call's other buffers):
+    ARTIS_ERR_HIP, and no caller array is written.  Without the limit the same engine solves the same block."""
+    ERR_HIP = -2  # include/artis_gpu.h
+    m, p, nt, arr = _multicell_case()
+    cells = arr.mgi_list
+    ao = arr.copy()
+    assert oracle_lib.update_grid_nlte(m, nt, ao, params=p, nthreads=16) == 0
+    eng = Engine(m, params=p)
+    try:
+        ag = arr.copy()
+        monkeypatch.setenv("ARTIS_GPU_FAIL_ALLOC_ABOVE", str(8 * int(nt.shells.sfpts) ** 2 // 2))
+        with pytest.raises(EngineError, match=f"update_grid_nlte -> {ERR_HIP}:"):
+            eng.update_grid_nlte(nt, ag)
+        monkeypatch.delenv("ARTIS_GPU_FAIL_ALLOC_ABOVE")
+        for k, v in _ndarrays(arr).items():
+            assert getattr(ag, k).tobytes() == v.tobytes(), k
+        ms = eng.update_grid_nlte(nt, ag)
+    finally:
+        eng.close()
+    print(f"after the refused allocation: gpu {ms:.1f} ms for {len(cells)} cells, passes {ag.iters[cells]}")
+    assert (ag.iters[cells][arr.thick[cells] == 1] == 0).all() and (ag.iters[cells][arr.thick[cells] != 1] > 0).all()
     _compare_physical(m, ao, ag, cells, te_rtol=1e-3, agg_tol=2e-2)
 
 
@@ -276,14 +315,9 @@ def test_update_grid_nlte_subset_roundtrip():
     print(f"subset: gpu {ms:.1f} ms for {len(arr.mgi_list)} cells")
     _compare_physical(m, ao, ag, arr.mgi_list, te_rtol=1e-3, agg_tol=2e-2)
     untouched = np.setdiff1d(np.arange(m.npts_model), arr.mgi_list)
-    for f in ("Te", "nne", "TR", "W", "nlte_pops", "groundlevelpop"):
-        g, b0 = getattr(ag, f), getattr(before, f)
-        if f in ("nlte_pops",):
-            assert np.array_equal(g.reshape(m.npts_model, -1)[untouched], b0.reshape(m.npts_model, -1)[untouched]), f
-        elif f == "groundlevelpop":
-            assert np.array_equal(g.reshape(m.npts_model, -1)[untouched], b0.reshape(m.npts_model, -1)[untouched]), f
-        else:
-            assert np.array_equal(g[untouched], b0[untouched]), f
+    for f in FIELDS + ("iters", "nt_timestep_last_solved"):
+        g, b0 = getattr(ag, f).reshape(m.npts_model, -1), getattr(before, f).reshape(m.npts_model, -1)
+        assert g[untouched].tobytes() == b0[untouched].tobytes(), f
 
 
 def test_transport_reads_the_gpu_solution():

@@ -1,0 +1,34 @@
+"""Host check of the tables update_grid's host drivers derive (artis_amd/csrc/engine/nlte_tables.h): the NLTE
+rate-matrix layout, the bf-heating level list, get_mean_binding_energy and the Spencer-Fano grid, shell and
+transition tables.  tests/nlte_tables_check.cpp includes that header alone and is built with hipcc for the host (no
+GPU needed); it runs once plain and once as a stand-alone executable under the host address / undefined
+sanitizers."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"]
+
+
+def _build(exe, extra):
+    return subprocess.run([HIPCC, "-std=c++17", "-O1", "-ffp-contract=off", *extra, "-I", os.path.join(REPO, "include"),
+                           "-I", os.path.join(REPO, "artis_amd", "csrc", "engine"), "-x", "c++",
+                           os.path.join(REPO, "tests", "nlte_tables_check.cpp"), "-o", str(exe)],
+                          capture_output=True, text=True, timeout=300)
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
+@pytest.mark.parametrize("sanitized", [False, True])
+def test_nlte_host_tables(tmp_path, sanitized):
+    exe = tmp_path / "nlte_tables_check"
+    b = _build(exe, SANITIZE if sanitized else [])
+    if sanitized and b.returncode != 0 and ("asan" in b.stderr or "ubsan" in b.stderr or "sanitizer" in b.stderr):
+        pytest.skip("the host sanitizer runtime is not installed")
+    assert b.returncode == 0, b.stderr
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "bad 0" in r.stdout
