@@ -1338,6 +1338,8 @@ int run_wavefront(int64_t n, int nts, double t2) {
   // counts in LDS; not with the binned R queue, which uses the same counts array)
   W.bin_push = W.ma_binned && G.knob.bin_push_on && !G.knob.r_binned && G.K.C.n_nonempty > 0 &&
                !(G.knob.ma_bin_blk && G.K.C.n_nonempty + 1 <= MA_BIN_LDS);
+  // k_ma parks a long launch's tail walks (row mode; only with tickets, WaveState::ma_park)
+  W.ma_park = (W.ma_tick && !G.K.C.ma_level_mode) ? G.knob.ma_park : 0;
   const unsigned grid = (unsigned)G.wave_grid;
   if (int rc = sync_ctx()) return rc;
   G.tev_used = 0;
@@ -1355,6 +1357,7 @@ int run_wavefront(int64_t n, int nts, double t2) {
   bool done = false;
   // the QX queue's length at the end of the round before last, as the host last read it (-1: not read yet)
   int64_t qx_known = -1;
+  uint32_t first_mq = 0;  // ARTIS_GPU_STATS: the M queue of the first round
   const bool first_placement = G.ma_initial_placement;
   for (; round < WAVE_MAX_ROUNDS && !done; round++) {
     // level mode: after the first rounds of a transport on the initial placement (and again a few rounds later),
@@ -1415,6 +1418,10 @@ int run_wavefront(int64_t n, int nts, double t2) {
         }))
       return rc;
     HIPCHK(hipMemsetAsync(W.ctr + 2 * QR, 0, 2 * sizeof(uint32_t), G.stream));
+    if (round == 0 && getenv("ARTIS_GPU_STATS")) {  // (diagnostic: the only queue length the host waits for)
+      HIPCHK(hipMemcpyAsync(&first_mq, W.ctr + 2 * QM, sizeof(first_mq), hipMemcpyDeviceToHost, G.stream));
+      HIPCHK(hipStreamSynchronize(G.stream));
+    }
     TSTART(4);  // class 4: the macro-atom queue binning (class 1 is k_ma alone)
     if (W.ma_binned) {
       const int nne = G.K.C.n_nonempty;
@@ -1454,7 +1461,14 @@ int run_wavefront(int64_t n, int nts, double t2) {
     else
       k_ma<1, false, false><<<ma_grid, WAVE_BLOCK, 0, G.stream>>>(G.d_ctx, W, G.d_soa, n, nts);
     TEND(1);
-    HIPCHK(hipMemsetAsync(W.ctr + 2 * QM, 0, 2 * sizeof(uint32_t), G.stream));
+    // the next round's M queue starts with the walks this launch parked: their count becomes the queue's (a parked
+    // walk is an M-queue entry like any other for the round loop's end below), and the count is zero again
+    if (W.ma_park) {
+      HIPCHK(hipMemcpyAsync(W.ctr + 2 * QM, W.ctr + 2 * QM + 1, sizeof(uint32_t), hipMemcpyDeviceToDevice, G.stream));
+      HIPCHK(hipMemsetAsync(W.ctr + 2 * QM + 1, 0, sizeof(uint32_t), G.stream));
+    } else {
+      HIPCHK(hipMemsetAsync(W.ctr + 2 * QM, 0, 2 * sizeof(uint32_t), G.stream));
+    }
     // jumps the 32-bit keys could not decide (rare), exact; walks go back to M.  Launched only when the queue may
     // hold any: in the first two rounds, and whenever the host's last reading (the round before last) found entries.
     // A round without the launch leaves its entries queued (QX is reset only after a launch) for a later one; the
@@ -1532,6 +1546,14 @@ int run_wavefront(int64_t n, int nts, double t2) {
               st[4 * c] ? (double)st[4 * c + 2] / st[4 * c] : 0., st[4 * c + 3] ? (double)st[4 * c] / st[4 * c + 3] : 0.,
               st[4 * c + 3] ? (double)st[16 + 4 * c] / st[4 * c + 3] : 0.,
               st[4 * c] ? (double)st[17 + 4 * c] / st[4 * c] : 0.);
+    // k_ma by phase: while the wave's queue still has walks for it, and after (the launch's tail)
+    fprintf(stderr,
+            "[artis_gpu] ma by phase: filled passes %llu, lane utilisation %.3f; tail passes %llu, lane utilisation %.3f; "
+            "idle lane-passes filled %llu, tail %llu; walks parked %llu (threshold %d, refill at %d idle lanes); first M "
+            "queue %u; rounds %lld\n",
+            st[4] - st[46], st[4] > st[46] ? (double)(st[5] - st[47]) / (64.0 * (st[4] - st[46])) : 0., st[46],
+            st[46] ? (double)st[47] / (64.0 * st[46]) : 0., 64 * (st[4] - st[46]) - (st[5] - st[47]),
+            64 * st[46] - st[47], st[28], W.ma_park, W.refill_ma, first_mq, (long long)round);
     fprintf(stderr,
             "[artis_gpu] rpkt per pass: lines scanned wave-max %.2f vs lane-mean %.3f; bf continua wave-max %.2f vs "
             "lane-mean %.3f\n",

@@ -33,7 +33,16 @@ namespace {
 //                       |                |                         |   (1e7-packet bench, before tickets: 32 idle lanes 2212 ms,
 //                       |                |                         |   16: 2064, 8: 2042; round 5, with the line-0 suffix and the
 //                       |                |                         |   F-queue records: 4: 2578 ms, 8: 1694, 12: 1559, 14: 1568,
-//                       |                |                         |   16: 1581, 20: 1617, 24: 1659; profiles/r5s_refill_sweep.txt)
+//                       |                |                         |   16: 1581, 20: 1617, 24: 1659; profiles/r5s_refill_sweep.txt;
+//                       |                |                         |   with MA_PARK=32: 8: 1379 ms, 12: 1230, 16: 1249,
+//                       |                |                         |   profiles/r7_ma_park_ab.txt)
+//   MA_PARK=<lanes>     | 32             | atoi clamped to 0..64   | k_ma parks the walks of a wave whose queue is used up and
+//                       |                |                         |   that has fewer busy lanes, for the next round (0: off;
+//                       |                |                         |   only in launches of >= 4 walks per lane, row mode with
+//                       |                |                         |   tickets).  1e7-packet bench, k_ma per step: parent 1441 ms,
+//                       |                |                         |   0: 1500, 8: 1285, 16: 1254, 24: 1237, 32: 1230, 40: 1227,
+//                       |                |                         |   48: 1240, 64: 1243; the step 2636 -> 2412 ms at 32
+//                       |                |                         |   (profiles/r7_ma_park_ab.txt)
 //   MA_OCC=8            | 1              | '8': 8, else 1          | k_ma minimum waves per SIMD (launch bounds)
 //   MA_WAVES=<w>        | 4              | atoi in 1..8, else 4    | k_ma blocks per CU: fewer concurrent walks thrash the
 //                       |                |                         |   caches less, the walk is bound by the memory system (1e7
@@ -73,6 +82,7 @@ struct Knobs {
   bool bin_push_on = true;  // M queue binned by its producers (WaveState::bin_push; off: k_ma_bin)
   bool ma_bin_blk = true;   // few cells: block-local M-queue binning (off: per-entry atomics)
   int refill_min = 32, refill_ma = 12;
+  int ma_park = MA_PARK_DEFAULT;  // WaveState::ma_park
   int ma_occ = 1;    // k_ma minimum waves per SIMD (launch bounds): 1 or 8
   int ma_waves = 4;  // k_ma blocks per CU
   int coop_max = 64;
@@ -119,6 +129,7 @@ inline Knobs read_knobs() {
   k.ma_bin_blk = !first_is("ARTIS_GPU_MA_BIN_BLK", '0');
   k.refill_min = lanes("ARTIS_GPU_REFILL", 32);
   k.refill_ma = lanes("ARTIS_GPU_REFILL_MA", 12);
+  if (const char *e = getenv("ARTIS_GPU_MA_PARK")) k.ma_park = std::max(0, std::min(64, atoi(e)));
   k.ma_occ = first_is("ARTIS_GPU_MA_OCC", '8') ? 8 : 1;
   if (const char *e = getenv("ARTIS_GPU_MA_WAVES")) {
     const int v = atoi(e);

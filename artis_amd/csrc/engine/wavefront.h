@@ -44,6 +44,10 @@ struct WaveState {
   int r_binned;        // 1: this k_rpkt launch reads the R queue binned by cell from ma_sorted (k_r_bin / k_r_scatter)
   int refill_min;      // a wave refetches work (and flushes its queue appends) once this many lanes are idle
   int refill_ma;       // the same for k_ma (a macro-atom refill is cheap: one coalesced ticket read)
+  int ma_park;         // k_ma: a wave whose queue is used up and whose busy lanes fall below this parks its walks
+                       // for the next round (ARTIS_GPU_MA_PARK; 0: every walk runs to its end in this launch).  The
+                       // parked walks are appended from slot 0 of the M queue with ctr[2 * QM + 1] as their count:
+                       // only with tickets (k_ma then reads none of the queue's own arrays)
   int coop_max;        // level mode: at most this many cooperative jumps per k_ma pass (the other lanes without a
                        // record wait for a later pass; ARTIS_GPU_MA_COOP_MAX, default 64 = all)
   // cell-sorted macro-atom tickets written by k_ma_scatter when the key cache is on (else nullptr): per slot
@@ -61,7 +65,10 @@ struct WaveState {
   unsigned long long *stats;  // [48] diagnostics: per kernel class c: [4c] wave loop passes, [4c+1] busy
                               // lane-passes, [4c+2] wave cycles (s_memtime), [4c+3] refills;
                               // [16 + 4c] cycles in refill blocks, [17 + 4c] cycles in the work step; [40] exact
-                              // jumps (k_ma_exact), [45] level mode: jumps made by the wave from the exact sums
+                              // jumps (k_ma_exact), [45] level mode: jumps made by the wave from the exact sums;
+                              // k_ma by phase: [46] passes and [47] busy lane-passes of waves whose queue was used
+                              // up (the launch's tail; the rest of [4], [5] is the filled phase), [28] walks parked
+                              // (counted in every build)
 };
 
 DEVFN int lane_id() { return (int)__lane_id(); }
@@ -116,9 +123,10 @@ DEVFN void wave_push(const WaveState &W, int q, bool pred, int32_t idx) {
 }
 // M-queue append with the walk's pre-ticket (WaveState::ma_pre): a new macro-atom activation of packet p
 // bin: the walk's M-queue bin (ma_push_bin), or -1 when the producers do not bin
-DEVFN void wave_push_ma(const WaveState &W, bool pred, int32_t idx, int where, int number, uint32_t rng_n, int4 b,
-                        int bin) {
-  const uint32_t slot = wave_reserve(&W.ctr[2 * QM], pred);
+// ctr: the queue's append counter, or ctr[2 * QM + 1] for the walks k_ma parks while it runs (WaveState::ma_park)
+DEVFN void wave_push_ma_at(const WaveState &W, uint32_t *ctr, bool pred, int32_t idx, int where, int number,
+                           uint32_t rng_n, int4 b, int bin) {
+  const uint32_t slot = wave_reserve(ctr, pred);
   if (pred) {
     W.q[QM][slot] = idx;
     if (bin >= 0) {
@@ -130,6 +138,10 @@ DEVFN void wave_push_ma(const WaveState &W, bool pred, int32_t idx, int where, i
       W.ma_pre[2 * (int64_t)slot + 1] = b;
     }
   }
+}
+DEVFN void wave_push_ma(const WaveState &W, bool pred, int32_t idx, int where, int number, uint32_t rng_n, int4 b,
+                        int bin) {
+  wave_push_ma_at(W, &W.ctr[2 * QM], pred, idx, where, number, rng_n, b, bin);
 }
 // F-queue append with the deactivation's record (WaveState::mf_rec)
 DEVFN void wave_push_mf(const WaveState &W, bool pred, int32_t idx, int4 e, uint32_t jumps, uint32_t rng_n) {
@@ -674,6 +686,14 @@ __global__ __launch_bounds__(WAVE_BLOCK) void k_ma_scatter_blk(const Ctx *__rest
 // COOP = false (row mode: every pair has a record) compiles without the cooperative jump.
 // LEVEL (level mode, DevCells::ma_lptr): a lane without a record -- or whose high key halves cannot decide -- makes
 // that jump in the wave's exact-sum path: inline in this pass (COOP), or parked on the QX queue for k_ma_exact.
+//
+// The tail of a long launch: once a wave's queue is used up it iterates until its longest walk ends, with ever fewer
+// busy lanes at the same cost per pass.  Below WaveState::ma_park busy lanes it parks the walks instead, as k_ma_exact
+// parks a walk between two jumps (level, jump count, RNG counter -> M queue): the next round bins them with its own
+// activations and walks them in full waves.  Only in a launch whose queue held MA_PARK_FILL walks per lane of the
+// grid, so the short rounds (the last ones, a small ensemble's) run every walk to its end and the rounds end.
+#define MA_PARK_FILL 4
+#define MA_PARK_DEFAULT 32  // the default of ARTIS_GPU_MA_PARK (engine_state.h)
 template <int MINW, bool COOP, bool LEVEL>
 __global__ __launch_bounds__(WAVE_BLOCK, MINW) void k_ma(const Ctx *__restrict__ ctxp, WaveState W,
                                                          const uint64_t *__restrict__ soa, int64_t n, int nts) {
@@ -705,6 +725,8 @@ __global__ __launch_bounds__(WAVE_BLOCK, MINW) void k_ma(const Ctx *__restrict__
   uint32_t fjumps = 0, frng = 0;
   unsigned long long jumps_sum = 0, trans_sum = 0, coop_sum = 0;
   unsigned long long st_pass = 0, st_busy = 0, st_refill = 0, st_trefill = 0, st_tstep = 0;
+  unsigned long long st_pass_tail = 0, st_busy_tail = 0, st_park = 0;
+  const bool park_on = W.ma_park > 0 && nq >= (uint32_t)MA_PARK_FILL * gridDim.x * WAVE_BLOCK;
 #ifdef ARTIS_STAMPS
   unsigned long long ma_st[4] = {0, 0, 0, 0};
   __shared__ unsigned long long s_diag[48];
@@ -788,6 +810,10 @@ __global__ __launch_bounds__(WAVE_BLOCK, MINW) void k_ma(const Ctx *__restrict__
     }
     st_pass++;
     st_busy += __popcll(__ballot(have));
+    if (ARTIS_WAVE_STATS && drained) {
+      st_pass_tail++;
+      st_busy_tail += __popcll(__ballot(have));
+    }
     const unsigned long long ts0 = wave_clock();
     // a lane whose current level has no record: its jump is made by the whole wave below
     const bool unc = LEVEL && have && mc.line == MA_NOLINE;
@@ -898,6 +924,28 @@ __global__ __launch_bounds__(WAVE_BLOCK, MINW) void k_ma(const Ctx *__restrict__
         have = false;
       }
     }
+    // the launch's tail: park the walks that stand between two jumps (a transition search in progress first runs to
+    // its end, MA_PENDING)
+    if (park_on && drained) {
+      const unsigned long long hm = __ballot(have);
+      if (hm && __popcll(hm) < W.ma_park) {
+        const bool park = have && r == MA_CONTINUE;
+        if (__any(park)) {
+          int where = 0;
+          if (park) {
+            where = lo32(soa[PW(n, idx, 0)]);
+            W.pend[idx] = make_int4(MA_RESUME, mc.ul, 0, 0);
+            W.pend_jumps[idx] = mc.jumps;
+            W.rng_n[idx] = rng.n;
+            trans_sum += mc.ntrans;
+            have = false;
+          }
+          wave_push_ma_at(W, &W.ctr[2 * QM + 1], park, idx, where, (int)rng.key1, rng.n, ma_pre_resume(mc.ul, mc.jumps),
+                          (W.bin_push && park) ? K.C.ma_bin[mc.k] : -1);
+          st_park += __popcll(__ballot(park));
+        }
+      }
+    }
     st_tstep += wave_clock() - ts0;
 #ifdef ARTIS_STAMPS
     // k_ma phases (cycles per pass): fetch (metadata + record lines in LDS), jump, the rest of the pass; with
@@ -927,6 +975,11 @@ __global__ __launch_bounds__(WAVE_BLOCK, MINW) void k_ma(const Ctx *__restrict__
     if (s_diag[j]) atomicAdd(&g_ma_diag[j], s_diag[j]);
 #endif
   wave_stats_flush(W, 1, st_pass, st_busy, st_t0, st_refill, st_trefill, st_tstep);
+  if (ARTIS_WAVE_STATS && lane_id() == 0) {
+    atomicAdd(&W.stats[46], st_pass_tail);
+    atomicAdd(&W.stats[47], st_busy_tail);
+  }
+  if (st_park && lane_id() == 0) atomicAdd(&W.stats[28], st_park);
   if (jumps_sum) atomicAdd(&s_work[WK_MA_JUMPS], jumps_sum);
   if (coop_sum) atomicAdd(&W.stats[45], coop_sum);  // (level mode: jumps made by the wave from the exact sums)
   if (trans_sum) atomicAdd(&s_work[WK_MA_TRANS], trans_sum);
