@@ -24,6 +24,7 @@ ABI_SYMBOLS = [
     "artis_gpu_estimators_download", "artis_gpu_estimator_block_doubles", "artis_gpu_estimator_block_to_device",
     "artis_gpu_estimator_block_from_device", "artis_gpu_last_transport_ms", "artis_gpu_last_precompute_ms",
     "artis_gpu_last_work_counts", "artis_gpu_last_rounds", "artis_gpu_spectrum", "artis_gpu_spectra", "artis_gpu_spectra_res",
+    "artis_gpu_line_trace",
     "artis_gpu_last_kernel_times",
     "artis_gpu_last_kernel_class_times", "artis_gpu_last_error", "artis_gpu_abi_version",
     "artis_gpu_vpkt_init", "artis_gpu_vpkt_zero", "artis_gpu_vpkt_download", "artis_gpu_vpkt_last_stats", "artis_gpu_vpkt_last_work",
@@ -82,6 +83,7 @@ def gpu_lib():
         L.artis_gpu_spectrum.argtypes = [C.c_int, C.c_int, vp, vp, vp]
         L.artis_gpu_spectra.argtypes = [C.POINTER(ffi.SpectraRequest), C.POINTER(ffi.SpectraOut)]
         L.artis_gpu_spectra_res.argtypes = [C.POINTER(ffi.SpectraResRequest), C.POINTER(ffi.SpectraOut)]
+        L.artis_gpu_line_trace.argtypes = [C.POINTER(ffi.LineTraceRequest), C.POINTER(ffi.LineTraceOut)]
         L.artis_gpu_vpkt_init.argtypes = [C.POINTER(ffi.VpktParams)]
         L.artis_gpu_vpkt_download.argtypes = [C.POINTER(ffi.VpktResult), C.c_int]
         L.artis_gpu_vpkt_last_stats.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -257,6 +259,16 @@ class Engine:
                                        abin_first, abin_count, with_average, emission_res, stokes)
         req = ffi.spectra_res_request(nnubins, nprocs, abin_first, abin_count, with_average, syn_dir)
         self._check(self.lib.artis_gpu_spectra_res(C.byref(req), C.byref(out.struct)), "spectra_res")
+        return out
+
+    def line_trace(self, regions, nnubins=1000, nprocs=1, abin=-1, syn_dir=(0., 0., 1.), out=None):
+        """The per-line emission / absorption trace of the resident packets (artis_gpu_line_trace) for the given
+        regions, (time_min_days, time_max_days, lambda_min_A, lambda_max_A) tuples: ADDED into out
+        (ffi.LineTraceArrays, made for the request when None)."""
+        if out is None:
+            out = ffi.LineTraceArrays(self.model.nlines, len(regions))
+        req = ffi.line_trace_request(regions, nnubins, nprocs, abin, syn_dir)
+        self._check(self.lib.artis_gpu_line_trace(C.byref(req), C.byref(out.struct)), "line_trace")
         return out
 
     # virtual packets (VPKT_ON)

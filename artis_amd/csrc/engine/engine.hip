@@ -1854,6 +1854,87 @@ int artis_gpu_spectra_res(const artis_spectra_res_request *req, artis_spectra_ou
   return 0;
 }
 
+// The per-line emission / absorption trace (k_line_trace): lines [nregions][nlines][4] and totals [nregions][2],
+// accumulated on the device per call and ADDED into the caller's arrays.
+int artis_gpu_line_trace(const artis_line_trace_request *req, artis_line_trace_out *out) {
+  if (!G.initialised) return ARTIS_ERR_NOT_INITIALISED;
+  if (!req || !out) {
+    G.last_error = "line_trace: NULL request or output";
+    return ARTIS_ERR_BAD_ARGUMENT;
+  }
+  if (!out->lines || !out->totals || !req->regions) {
+    G.last_error = "line_trace: NULL lines, totals or regions";
+    return ARTIS_ERR_BAD_ARGUMENT;
+  }
+  if (req->nnubins <= 0 || req->nprocs <= 0 || req->abin < -1 || req->abin >= ARTIS_MABINS || req->nregions < 1 ||
+      req->nregions > ARTIS_LINE_TRACE_MAX_REGIONS) {
+    G.last_error = "line_trace: bad request (nnubins, nprocs > 0; abin in [-1, ARTIS_MABINS); nregions in "
+                   "[1, ARTIS_LINE_TRACE_MAX_REGIONS])";
+    return ARTIS_ERR_BAD_ARGUMENT;
+  }
+  for (int r = 0; r < req->nregions; r++) {
+    const artis_line_trace_region &R = req->regions[r];
+    if (!std::isfinite(R.nu_lower) || !std::isfinite(R.nu_upper) || !std::isfinite(R.time_min) ||
+        !std::isfinite(R.time_max) || R.nu_lower > R.nu_upper || R.time_min > R.time_max) {
+      G.last_error = "line_trace: region " + std::to_string(r) +
+                     " has a non-finite bound, nu_lower > nu_upper or time_min > time_max";
+      return ARTIS_ERR_BAD_ARGUMENT;
+    }
+  }
+  const int nnb = req->nnubins, nreg = req->nregions;
+  const double nu_min = G.K.G.nu_min_r, nu_max = G.K.G.nu_max_r;
+  const double dlognu = (log(nu_max) - log(nu_min)) / nnb;  // spectrum.cc:352, 491-500 (host libm)
+  std::vector<double> delta(nnb);
+  for (int nnu = 0; nnu < nnb; nnu++)
+    delta[nnu] = spec_delta_freq(nu_min, dlognu, nnu);
+  const size_t nlin = (size_t)nreg * G.nlines * 4, ntot = (size_t)nreg * 2;
+  const size_t total = nnb + nlin + ntot;  // delta_freq first, then lines, then totals
+  DevBufs B;  // released on every path
+  double *d = nullptr;
+  if (int rc = B.get(&d, total, (const double *)nullptr)) {
+    (void)hipGetLastError();  // the failed allocation is reported here, not by the next launch check
+    G.last_error = "line_trace: out of device memory: allocating " + std::to_string(total * sizeof(double)) +
+                   " bytes of accumulators failed; ask for fewer regions per call";
+    return rc;
+  }
+  if (int rc = sync_ctx()) return rc;
+  HIPCHK(hipMemsetAsync(d + nnb, 0, (nlin + ntot) * sizeof(double), G.stream));
+  HIPCHK(hipMemcpyAsync(d, delta.data(), nnb * sizeof(double), hipMemcpyHostToDevice, G.stream));
+  LineTraceArgs A{};
+  A.nnubins = nnb;
+  A.nprocs = req->nprocs;
+  A.abin = req->abin;
+  A.ntstep = G.ntstep;
+  A.nregions = nreg;
+  A.nlines = G.nlines;
+  for (int k = 0; k < 3; k++) A.syn_dir[k] = req->syn_dir[k];
+  A.dlognu = dlognu;
+  A.delta_freq = d;
+  A.lines = d + nnb;
+  A.totals = d + nnb + nlin;
+  for (int r = 0; r < nreg; r++) A.regions[r] = req->regions[r];
+  if (G.npkts > 0)
+    k_line_trace<<<(unsigned)((G.npkts + 255) / 256), 256, 0, G.stream>>>(G.d_ctx, G.d_soa, G.npkts, A);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(G.stream));  // a kernel fault is reported before anything is added to the caller's arrays
+  // copy back through a small staging buffer that stays warm, and ADD (lines and totals are contiguous on the device)
+  constexpr size_t STAGE = (size_t)1 << 19;  // doubles (4 MiB)
+  std::vector<double> h(std::min(STAGE, nlin + ntot));
+  for (size_t o = 0; o < nlin + ntot; o += STAGE) {
+    const size_t m = std::min(STAGE, nlin + ntot - o);
+    HIPCHK(hipMemcpyAsync(h.data(), d + nnb + o, m * sizeof(double), hipMemcpyDeviceToHost, G.stream));
+    HIPCHK(hipStreamSynchronize(G.stream));
+    for (size_t j = 0; j < m; j++) {
+      const size_t g = o + j;
+      if (g < nlin)
+        out->lines[g] += h[j];
+      else
+        out->totals[g - nlin] += h[j];
+    }
+  }
+  return 0;
+}
+
 int artis_gpu_vpkt_init(const artis_vpkt_params *vp) {
   if (!G.initialised) return ARTIS_ERR_NOT_INITIALISED;
   if (!vp || vp->nobs <= 0 || vp->nspectra <= 0 || vp->nspectra > ARTIS_VPKT_MAX_SPECTRA || vp->nrange < 0 ||

@@ -242,4 +242,109 @@ __global__ void k_spectra_res(const Ctx *__restrict__ ctxp, const uint64_t *__re
   }
 }
 
+// ---- the per-line emission / absorption trace (spectrum.cc:11-30, 395-408, 435-447, 454-468) --------------------
+// TRACE_EMISSION_ABSORPTION_REGION_ON of add_to_spec for up to ARTIS_LINE_TRACE_MAX_REGIONS (time, frequency) windows
+// in one pass: lines[region][line] is one struct emissionabsorptioncontrib (32 bytes: the two emission sums in one
+// 16-byte half, the two absorption sums in the other), totals[region] = traceemission_totalenergy,
+// traceabsorption_totalenergy.  The windows travel by value in the kernel arguments.
+struct LineTraceArgs {
+  int nnubins, nprocs, abin, ntstep, nregions, nlines;
+  double syn_dir[3];
+  double dlognu;
+  const double *delta_freq;  // [nnubins] (init_spectra, host libm)
+  double *lines;             // [nregions][nlines][4]
+  double *totals;            // [nregions][2]
+  artis_line_trace_region regions[ARTIS_LINE_TRACE_MAX_REGIONS];
+};
+
+// The sum of v over the wave, in every lane.  All 64 lanes must call it.
+DEVFN double wave_sum(double v) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// One thread per packet.  A thread without a contribution (past the end, not an escaped r-packet, outside the
+// direction bin, refused by add_to_spec's admission test, in no window) keeps running with an empty window mask:
+// the per-window totals are summed across the wave (one atomic per wave, window and total instead of one per
+// packet on a single address), and the cross-lane sum needs all 64 lanes.  A window no lane of the wave lies in is
+// skipped by a wave-uniform branch.  log(nu_rf), the timestep and deltaE are evaluated once per packet; the trace's
+// own words (19, 21, 14-17, 35) are read only by a packet that lies in a window.
+__global__ void k_line_trace(const Ctx *__restrict__ ctxp, const uint64_t *__restrict__ soa, int64_t n,
+                             LineTraceArgs A) {
+  const Ctx &K = *ctxp;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t inwin = 0;  // bit r: the packet lies in window r
+  double deltaE = 0., nu_rf = 0., t_arrive = 0., e_rf = 0.;
+  int nt = -1;
+  SpecPkt P;
+  if (i < n && spec_load(K, soa, n, i, P) && P.escape_type == ARTIS_TYPE_RPKT &&
+      (A.abin < 0 || escapedirectionbin(P.dir, A.syn_dir) == A.abin)) {
+    // spectrum.cc:346-360 add_to_spec, as spec_add_rpkt
+    const double anglefactor = (A.abin >= 0) ? ARTIS_MABINS : 1.;
+    const double tmin = K.G.tmin, tmax = K.G.tmax;
+    const double nu_min = K.G.nu_min_r, nu_max = K.G.nu_max_r;
+    t_arrive = P.t_arrive;
+    e_rf = P.e_rf;
+    nu_rf = asd(soa[PW(n, i, 12)]);
+    if (t_arrive > tmin && t_arrive < tmax && nu_rf > nu_min && nu_rf < nu_max) {
+      nt = spec_timestep(K, A.ntstep, t_arrive);
+      const int nnu = (int)((log(nu_rf) - log(nu_min)) / A.dlognu);
+      if (nt >= 0 && nnu >= 0 && nnu < A.nnubins) {
+        deltaE = e_rf / K.G.ts_width[nt] / A.delta_freq[nnu] / 4.e12 / ARTIS_PI / ARTIS_PARSEC / ARTIS_PARSEC /
+                 A.nprocs * anglefactor;
+        // spectrum.cc:398-399, 435-438: both bounds inclusive
+        for (int r = 0; r < A.nregions; r++) {
+          const artis_line_trace_region &R = A.regions[r];
+          if (t_arrive >= R.time_min && t_arrive <= R.time_max && nu_rf >= R.nu_lower && nu_rf <= R.nu_upper)
+            inwin |= 1u << r;
+        }
+      }
+    }
+  }
+  int et = -1, at = -1;
+  double vem = 0., deltaE_absorption = 0., vab = 0.;
+  if (inwin) {
+    const uint64_t w19 = soa[PW(n, i, 19)];
+    et = hi32(w19);
+    if (et >= A.nlines) et = -1;  // no such line: never written by the transport
+    if (et >= 0) vem = (double)__int_as_float(hi32(soa[PW(n, i, 35)])) * deltaE;  // spectrum.cc:402
+    // spectrum.cc:410-416
+    const double absorptionfreq = asd(soa[PW(n, i, 21)]);
+    const int nnu_abs = (int)((log(absorptionfreq) - log(K.G.nu_min_r)) / A.dlognu);
+    at = lo32(w19);
+    if (!(nnu_abs >= 0 && nnu_abs < A.nnubins) || at >= A.nlines) at = -1;
+    if (at >= 0) {
+      const double anglefactor = (A.abin >= 0) ? ARTIS_MABINS : 1.;
+      deltaE_absorption = e_rf / K.G.ts_width[nt] / A.delta_freq[nnu_abs] / 4.e12 / ARTIS_PI / ARTIS_PARSEC /
+                          ARTIS_PARSEC / A.nprocs * anglefactor;
+      // spectrum.cc:441-443: get_velocity at em_pos, em_time, then vec_len
+      const double em_time = lo32(soa[PW(n, i, 17)]);
+      const double vel[3] = {asd(soa[PW(n, i, 14)]) / em_time, asd(soa[PW(n, i, 15)]) / em_time,
+                             asd(soa[PW(n, i, 16)]) / em_time};
+      vab = vec_len(vel) * deltaE_absorption;
+    }
+  }
+  const double em = (et >= 0) ? deltaE : 0., ab = (at >= 0) ? deltaE_absorption : 0.;
+  const int lane = threadIdx.x & 63;
+  for (int r = 0; r < A.nregions; r++) {
+    const bool in = (inwin >> r) & 1u;
+    if (__ballot(in) == 0) continue;  // wave-uniform
+    if (in && et >= 0) {
+      double *rec = A.lines + ((int64_t)r * A.nlines + et) * 4;
+      unsafeAtomicAdd(rec + 0, deltaE);
+      unsafeAtomicAdd(rec + 1, vem);
+    }
+    if (in && at >= 0) {
+      double *rec = A.lines + ((int64_t)r * A.nlines + at) * 4;
+      unsafeAtomicAdd(rec + 2, deltaE_absorption);
+      unsafeAtomicAdd(rec + 3, vab);
+    }
+    const double sum_em = wave_sum(in ? em : 0.), sum_ab = wave_sum(in ? ab : 0.);
+    if (lane == 0) {
+      if (sum_em != 0.) unsafeAtomicAdd(&A.totals[2 * r + 0], sum_em);
+      if (sum_ab != 0.) unsafeAtomicAdd(&A.totals[2 * r + 1], sum_ab);
+    }
+  }
+}
+
 #endif

@@ -3,6 +3,7 @@
 
 #include "artis_constants.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -670,6 +671,80 @@ int artis_write_light_curve(const char *lc_filename, int abin, int numtimesteps,
     for (int m = 0; m < numtimesteps; m++) {
       const double gd = gamma_dep ? gamma_dep[m] : 0., cl = cmf_lum ? cmf_lum[m] : 0.;
       fprintf(f.f, "%g %g %g\n", ts_mid[m] / kDay, (gd / kLsun / ts_width[m]), (cl / ts_width[m] / kLsun));
+    }
+  }
+  return 0;
+}
+
+// ---- the per-line emission / absorption trace (spectrum.cc:34-136 printout_tracemission_stats) ------------------
+int artis_rank_line_trace(const double *lines, int nlines, int column, int maxlines, int32_t *ranked) {
+  if (!lines || !ranked || nlines < 0 || maxlines < 0 || (column != 0 && column != 2)) return -1;
+  // compare_emission / compare_absorption (spectrum.cc:34-56) order by descending energy and the printing loop stops
+  // at the first line without energy (spectrum.cc:93, 128-129): only lines with energy > 0 can be listed.  qsort
+  // leaves the order of equal energies open; here the lower line index comes first.
+  std::vector<int32_t> idx;
+  for (int i = 0; i < nlines; i++)
+    if (lines[(size_t)i * 4 + column] > 0.) idx.push_back(i);
+  std::sort(idx.begin(), idx.end(), [&](int32_t a, int32_t b) {
+    const double ea = lines[(size_t)a * 4 + column], eb = lines[(size_t)b * 4 + column];
+    return ea > eb || (ea == eb && a < b);
+  });
+  const int n = (int)std::min<size_t>(idx.size(), (size_t)maxlines);
+  std::copy(idx.begin(), idx.begin() + n, ranked);
+  return n;
+}
+
+int artis_write_line_trace(const char *filename, const artis_atomic_tables *at, int nregions,
+                           const artis_line_trace_region *regions, const double *lines, const double *totals) {
+  if (!filename || !at || !regions || !lines || !totals || nregions < 0) return -1;
+  FileCloser f;
+  f.f = fopen(filename, "w");
+  if (!f.f) return -1;
+  const int maxlinesprinted = 500;
+  const int nlines = at->nlines;
+  std::vector<int32_t> ranked(maxlinesprinted);
+  for (int r = 0; r < nregions; r++) {
+    const artis_line_trace_region &R = regions[r];
+    const double *L = lines + (size_t)r * nlines * 4;
+    const double lambdamin = 1e8 * ARTIS_CLIGHT / R.nu_upper, lambdamax = 1e8 * ARTIS_CLIGHT / R.nu_lower;
+    // mode is 0 for emission and 1 for absorption
+    for (int mode = 0; mode < 2; mode++) {
+      const double totalenergy = totals[2 * r + mode];
+      if (mode == 0) {
+        fprintf(f.f, "lambda [%5.1f, %5.1f] nu %g %g\n", lambdamin, lambdamax, R.nu_lower, R.nu_upper);
+        fprintf(f.f, "Top line emission contributions in the range lambda [%5.1f, %5.1f] time [%5.1fd, %5.1fd] (%g erg)\n",
+                lambdamin, lambdamax, R.time_min / kDay, R.time_max / kDay, totalenergy);
+      } else {
+        fprintf(f.f,
+                "Top line absorption contributions in the range lambda [%5.1f, %5.1f] time [%5.1fd, %5.1fd] (%g erg)\n",
+                lambdamin, lambdamax, R.time_min / kDay, R.time_max / kDay, totalenergy);
+      }
+      fprintf(f.f, "%17s %4s %9s %5s %5s %8s %8s %4s %7s %7s %7s %7s\n", "energy", "Z", "ion_stage", "upper", "lower",
+              "coll_str", "A", "forb", "lambda", "<v_rad>", "B_lu", "B_ul");
+      const int n = artis_rank_line_trace(L, nlines, 2 * mode, maxlinesprinted, ranked.data());
+      for (int i = 0; i < n; i++) {
+        const int lineindex = ranked[i];
+        const double encontrib = L[(size_t)lineindex * 4 + 2 * mode];
+        const int element = at->line_elementindex[lineindex];
+        const int ion = at->line_ionindex[lineindex];
+        const int uion = at->elem_uniqueionoffset[element] + ion;
+        const double linelambda = 1e8 * ARTIS_CLIGHT / at->line_nu[lineindex];
+        // flux-weighted average radial velocity of emission (absorption) in km/s
+        const double v_rad = L[(size_t)lineindex * 4 + 2 * mode + 1] / encontrib / 1e5;
+        const int lower = at->line_lowerlevelindex[lineindex];
+        const int upper = at->line_upperlevelindex[lineindex];
+        const int lev0 = at->ion_uniqueleveloffset[uion];
+        const double statweight_target = at->level_stat_weight[lev0 + upper];
+        const double statweight_lower = at->level_stat_weight[lev0 + lower];
+        const double nu_trans = (at->level_epsilon[lev0 + upper] - at->level_epsilon[lev0 + lower]) / ARTIS_H;
+        const double A_ul = at->line_einstein_A[lineindex];
+        const double B_ul = ARTIS_CLIGHTSQUAREDOVERTWOH / pow(nu_trans, 3) * A_ul;
+        const double B_lu = statweight_target / statweight_lower * B_ul;
+        fprintf(f.f, "%7.2e (%5.1f%%) %4d %9d %5d %5d %8.1f %8.2e %4d %7.1f %7.1f %7.1e %7.1e\n", encontrib,
+                100 * encontrib / totalenergy, at->elem_anumber[element], at->ion_ionstage[uion], upper, lower,
+                at->line_coll_str[lineindex], A_ul, (int)at->line_forbidden[lineindex], linelambda, v_rad, B_lu, B_ul);
+      }
+      fprintf(f.f, "\n");
     }
   }
   return 0;

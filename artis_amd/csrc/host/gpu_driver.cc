@@ -19,6 +19,9 @@
 // absorption.out, specpol.out, emissionpol.out, absorptionpol.out, gamma_spec.out and their _res_00 .. _res_99
 // forms (do_emission_res and POL_ON; observer direction syn_dir = z).  ARTIS_DRIVER_EXSPEC_NNUBINS=<n> replaces
 // the reference's 1000 frequency bins (MNUBINS), for small test runs.
+// ARTIS_DRIVER_EXSPEC_TRACE="tmin_d,tmax_d,lmin_A,lmax_A[;...]" (only with ARTIS_DRIVER_EXSPEC): also the per-line
+// emission / absorption trace of those regions (days and Angstroms, as the reference's traceemissabs_ defines;
+// PacketEngine::line_trace) into <dir>/emission_absorption_trace.out.
 #include <sys/stat.h>
 
 #include <algorithm>
@@ -29,6 +32,7 @@
 #include <string>
 #include <vector>
 
+#include "artis_constants.h"
 #include "artis_io.h"
 #include "artis_layout_check.h"
 #include "model_synth.h"
@@ -232,6 +236,40 @@ void write_exspec(artis_amd::PacketEngine &engine, const std::string &dir, const
     first += count;
   }
 }
+// ARTIS_DRIVER_EXSPEC_TRACE: "tmin_d,tmax_d,lmin_A,lmax_A[;...]" -> regions in Hz and s with the reference's
+// expressions (spectrum.cc:13-18).  false: not four numbers per region, or more regions than one call takes.
+bool parse_trace_regions(const char *spec, std::vector<artis_line_trace_region> &regions) {
+  std::string s(spec);
+  for (size_t pos = 0; pos <= s.size();) {
+    const size_t end = std::min(s.find(';', pos), s.size());
+    const std::string item = s.substr(pos, end - pos);
+    pos = end + 1;
+    if (item.empty()) continue;
+    double tmin_d, tmax_d, lmin, lmax;
+    char tail;
+    if (std::sscanf(item.c_str(), "%lf,%lf,%lf,%lf%c", &tmin_d, &tmax_d, &lmin, &lmax, &tail) != 4) return false;
+    regions.push_back({1.e8 * ARTIS_CLIGHT / lmax, 1.e8 * ARTIS_CLIGHT / lmin, tmin_d * ARTIS_DAY, tmax_d * ARTIS_DAY});
+  }
+  return !regions.empty() && regions.size() <= ARTIS_LINE_TRACE_MAX_REGIONS;
+}
+// the per-line emission / absorption trace of the same packets (PacketEngine::line_trace, angle average) and its
+// tables, emission_absorption_trace.out beside the exspec files
+void write_exspec_trace(artis_amd::PacketEngine &engine, const std::string &dir, const artis_atomic_tables &at,
+                        int nnubins, const double syn_dir[3], const std::vector<artis_line_trace_region> &regions) {
+  std::vector<double> lines(regions.size() * (size_t)at.nlines * 4, 0.), totals(regions.size() * 2, 0.);
+  artis_line_trace_request req{};
+  req.nnubins = nnubins;
+  req.nprocs = 1;
+  req.abin = -1;
+  req.nregions = (int32_t)regions.size();
+  for (int k = 0; k < 3; k++) req.syn_dir[k] = syn_dir[k];
+  req.regions = regions.data();
+  artis_line_trace_out out{lines.data(), totals.data()};
+  engine.line_trace(req, out);
+  artis_amd::check(artis_write_line_trace((dir + "/emission_absorption_trace.out").c_str(), &at, req.nregions,
+                                          regions.data(), lines.data(), totals.data()),
+                   "write_line_trace");
+}
 template <typename T>
 void put(std::ofstream &o, const std::vector<T> &v) {
   const int64_t n = (int64_t)v.size();
@@ -345,6 +383,17 @@ int main(int argc, char **argv) {
       write_exspec(engine, exs, at, *artis_model_geometry(m), cfg.nshells_1d > 0, nnubins, syn_dir, ts_gamma_dep,
                    ts_cmf_lum);
       std::printf("exspec written to %s\n", exs);
+      const char *trc = std::getenv("ARTIS_DRIVER_EXSPEC_TRACE");
+      if (trc && trc[0]) {
+        std::vector<artis_line_trace_region> regions;
+        if (!parse_trace_regions(trc, regions)) {
+          std::fprintf(stderr, "ARTIS_DRIVER_EXSPEC_TRACE: expected \"tmin_d,tmax_d,lmin_A,lmax_A[;...]\", at most %d "
+                               "regions\n", ARTIS_LINE_TRACE_MAX_REGIONS);
+          return 2;
+        }
+        write_exspec_trace(engine, exs, at, nnubins, syn_dir, regions);
+        std::printf("line trace of %zu regions written to %s\n", regions.size(), exs);
+      }
     }
     const char *tev = std::getenv("ARTIS_DRIVER_TE");
     if (tev && tev[0] == '1' && last_nts >= 0 && last_nts + 1 >= cfg.ntstep) {

@@ -73,6 +73,10 @@ void PacketEngine::spectra_res(const artis_spectra_res_request &request, artis_s
   check(artis_gpu_spectra_res(&request, &out), "artis_gpu_spectra_res");
 }
 
+void PacketEngine::line_trace(const artis_line_trace_request &request, artis_line_trace_out &out) {
+  check(artis_gpu_line_trace(&request, &out), "artis_gpu_line_trace");
+}
+
 double PacketEngine::last_transport_ms() const { return artis_gpu_last_transport_ms(); }
 
 }  // namespace artis_amd

@@ -59,6 +59,9 @@ class PacketEngine {
   // request in one pass (artis_gpu_spectra_res): results are ADDED into out's arrays, which carry the leading slot
   // dimension.  Aborts like every other call here, also when the device accumulators do not fit: ask for fewer bins.
   void spectra_res(const artis_spectra_res_request &request, artis_spectra_out &out);
+  // the per-line emission / absorption trace of those packets for the request's regions (artis_gpu_line_trace,
+  // spectrum.cc:395-447): ADDED into out.lines [nregions][nlines][4] and out.totals [nregions][2]
+  void line_trace(const artis_line_trace_request &request, artis_line_trace_out &out);
 
   double last_transport_ms() const;
 };

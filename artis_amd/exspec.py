@@ -3,9 +3,12 @@ the 100 line-of-sight sets (spec_res_XX.out, light_curve_res_XX.out, emission_re
 
 run() bins the engine's resident packets, or a list of rank packet files / arrays, with Engine.spectra_res -- one
 pass per packet set and chunk of direction bins -- and write_outputs() writes a block of slots with the C++ writers
-of libartis_io under the reference's file names.  Not reproduced: the emission / absorption trace of
-TRACE_EMISSION_ABSORPTION_REGION_ON (spectrum.cc:17-142).
+of libartis_io under the reference's file names.  With trace_regions, run() also takes the per-line emission /
+absorption trace of TRACE_EMISSION_ABSORPTION_REGION_ON (spectrum.cc:11-142, 395-447) for those regions in every
+packet set's pass (Engine.line_trace) and writes its tables to emission_absorption_trace.out (write_line_trace); the
+reference prints them into its log, so that file name is this project's.
 """
+import ctypes as C
 import os
 
 import numpy as np
@@ -28,6 +31,7 @@ RES_FILES = ("light_curve_res_%.2d.out", "spec_res_%.2d.out")
 RES_EMISSION_FILES = ("emission_res_%.2d.out", "emissiontrue_res_%.2d.out", "absorption_res_%.2d.out")
 RES_POL_FILES = ("specpol_res_%.2d.out",)
 RES_POL_EMISSION_FILES = ("emissionpol_res_%.2d.out", "absorptionpol_res_%.2d.out")
+LINE_TRACE_FILE = "emission_absorption_trace.out"
 
 
 def is_1d_read(model):
@@ -169,6 +173,44 @@ def write_outputs(outdir, model, arrays, emission_res=None, stokes=None, gamma_d
     return sorted(written)
 
 
+def rank_line_trace(lines_region, column, maxlines=500):
+    """The line indices of one region's lines [nlines, 4] in the order printout_tracemission_stats lists them
+    (spectrum.cc:58-136): descending energy of `column` (0 emission, 2 absorption), equal energies by ascending line
+    index, at most maxlines, only lines with energy > 0."""
+    a = np.ascontiguousarray(lines_region, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise ValueError("rank_line_trace: lines_region must be [nlines, 4]")
+    L = aio.lib()
+    L.artis_rank_line_trace.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+    ranked = np.zeros(max(int(maxlines), 1), dtype=np.int32)
+    n = L.artis_rank_line_trace(a.ctypes.data_as(C.POINTER(C.c_double)), a.shape[0], int(column), int(maxlines),
+                                ranked.ctypes.data_as(C.POINTER(C.c_int32)))
+    if n < 0:
+        raise ValueError(f"rank_line_trace: column {column} (0 or 2), maxlines {maxlines} (>= 0)")
+    return ranked[:n].copy()
+
+
+def write_line_trace(path, model, arrays, regions):
+    """The tables of printout_tracemission_stats (spectrum.cc:58-136) for every region of `arrays`
+    (ffi.LineTraceArrays), one block per region, with the C++ writer artis_write_line_trace.  regions: the
+    (time_min_days, time_max_days, lambda_min_A, lambda_max_A) tuples the arrays were taken for."""
+    regions = list(regions)
+    if len(regions) != arrays.nregions or arrays.nlines != model.nlines:
+        raise ValueError("write_line_trace: arrays do not belong to these regions / this model")
+    regs = (ffi.LineTraceRegion * max(len(regions), 1))()
+    for k, reg in enumerate(regions):
+        regs[k].nu_lower, regs[k].nu_upper, regs[k].time_min, regs[k].time_max = ffi.line_trace_region(*reg)
+    L = aio.lib()
+    dp = C.POINTER(C.c_double)
+    L.artis_write_line_trace.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.POINTER(ffi.LineTraceRegion), dp, dp]
+    lines = np.ascontiguousarray(arrays.lines, dtype=np.float64)
+    totals = np.ascontiguousarray(arrays.totals, dtype=np.float64)
+    rc = L.artis_write_line_trace(os.fspath(path).encode(), model.atomic, len(regions), regs,
+                                  lines.ctypes.data_as(dp), totals.ctypes.data_as(dp))
+    if rc != 0:
+        raise OSError(f"artis_write_line_trace({path}) -> {rc}")
+
+
 def load_packets(source):
     """One packet set: a PACKET_DTYPE array as it is, a raw packets_RRRR_tsN.tmp file (sn3d.cc:387-398), or a text
     packetsXX_RRRR.out file (packet.cc:152-196; %g precision)."""
@@ -187,7 +229,7 @@ def load_packets(source):
 
 
 def run(engine, outdir, packet_sources=None, nnubins=1000, syn_dir=(0., 0., 1.), emission_res=True, stokes=False,
-        max_bytes=None, gamma_dep=None, cmf_lum=None):
+        max_bytes=None, gamma_dep=None, cmf_lum=None, trace_regions=None):
     """The body of exspec.cc:140-263: bin and write the angle-averaged files and, for a 3D model, the 100
     direction-bin sets into outdir.
 
@@ -196,7 +238,12 @@ def run(engine, outdir, packet_sources=None, nnubins=1000, syn_dir=(0., 0., 1.),
     (the rank loop of exspec.cc:162; the engine's resident packets are then the last source).  The direction bins are
     taken in chunks whose host arrays stay within max_bytes (default: default_max_bytes()); with more than one chunk
     every source is uploaded once per chunk.  Returns (sorted names written, the arrays of the first chunk -- the
-    whole result when one chunk was enough)."""
+    whole result when one chunk was enough).
+
+    trace_regions: (time_min_days, time_max_days, lambda_min_A, lambda_max_A) tuples.  When given, every source's
+    pass of the first chunk also takes the per-line emission / absorption trace of those regions (Engine.line_trace,
+    angle-averaged, the same nnubins and nprocs), emission_absorption_trace.out is written into outdir and named in
+    the list, and the ffi.LineTraceArrays are returned as a third value."""
     model = engine.model
     nt = model.cfg.ntstep
     nbins = 0 if is_1d_read(model) else ffi.MABINS
@@ -211,6 +258,10 @@ def run(engine, outdir, packet_sources=None, nnubins=1000, syn_dir=(0., 0., 1.),
     if packet_sources is not None and not reload:
         engine.upload(load_packets(sources[0]))
     written, first = [], None
+    trace = None
+    if trace_regions is not None:
+        trace_regions = list(trace_regions)
+        trace = ffi.LineTraceArrays(model.nlines, len(trace_regions))
     for abin_first, abin_count, with_average in chunks:
         arrays = ffi.SpectraResArrays(nt, nnubins, model.nelements, model.maxnions, abin_first, abin_count,
                                       with_average, emission_res, stokes)
@@ -219,7 +270,13 @@ def run(engine, outdir, packet_sources=None, nnubins=1000, syn_dir=(0., 0., 1.),
                 engine.upload(load_packets(src))
             engine.spectra_res(nnubins=nnubins, nprocs=nprocs, abin_first=abin_first, abin_count=abin_count,
                                with_average=with_average, syn_dir=syn_dir, out=arrays)
+            if trace is not None and first is None:
+                engine.line_trace(trace_regions, nnubins=nnubins, nprocs=nprocs, abin=-1, syn_dir=syn_dir, out=trace)
         written += write_outputs(outdir, model, arrays, gamma_dep=gamma_dep, cmf_lum=cmf_lum)
         if first is None:
             first = arrays
-    return sorted(written), first
+    if trace is None:
+        return sorted(written), first
+    write_line_trace(os.path.join(os.fspath(outdir), LINE_TRACE_FILE), model, trace, trace_regions)
+    written.append(LINE_TRACE_FILE)
+    return sorted(written), first, trace

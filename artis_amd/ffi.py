@@ -537,6 +537,63 @@ def spectra_res_request(nnubins=1000, nprocs=1, abin_first=0, abin_count=MABINS,
     return r
 
 
+# the per-line emission / absorption trace (include/artis_gpu.h artis_line_trace_*)
+LINE_TRACE_MAX_REGIONS = 16
+LINE_TRACE_COLUMNS = ("energyemitted", "emission_weightedvelocity_sum", "energyabsorbed",
+                      "absorption_weightedvelocity_sum")
+
+
+class LineTraceRegion(C.Structure):
+    _fields_ = [("nu_lower", C.c_double), ("nu_upper", C.c_double), ("time_min", C.c_double),
+                ("time_max", C.c_double)]
+
+
+class LineTraceRequest(C.Structure):
+    _fields_ = [("nnubins", C.c_int32), ("nprocs", C.c_int32), ("abin", C.c_int32), ("nregions", C.c_int32),
+                ("syn_dir", C.c_double * 3), ("regions", C.POINTER(LineTraceRegion))]
+
+
+class LineTraceOut(C.Structure):
+    _fields_ = [("lines", C.POINTER(C.c_double)), ("totals", C.POINTER(C.c_double))]
+
+
+class LineTraceArrays:
+    """Host storage of one artis_line_trace_out: lines [nregions, nlines, 4] (LINE_TRACE_COLUMNS, the reference's
+    struct emissionabsorptioncontrib per line) and totals [nregions, 2] (emission, absorption)."""
+
+    def __init__(self, nlines, nregions):
+        self.nlines, self.nregions = int(nlines), int(nregions)
+        self.lines = np.zeros((self.nregions, self.nlines, 4))
+        self.totals = np.zeros((self.nregions, 2))
+        self.struct = LineTraceOut()
+        self.struct.lines = self.lines.ctypes.data_as(C.POINTER(C.c_double))
+        self.struct.totals = self.totals.ctypes.data_as(C.POINTER(C.c_double))
+
+    def arrays(self):
+        return {"lines": self.lines, "totals": self.totals}
+
+
+def line_trace_region(time_min_days, time_max_days, lambda_min_A, lambda_max_A):
+    """(nu_lower, nu_upper, time_min, time_max) in Hz and s of a region given in the units of the reference's
+    defines, with their expressions (spectrum.cc:13-18): nu = 1e8 CLIGHT / lambda, t = days * DAY."""
+    return (1.e8 * CLIGHT / lambda_max_A, 1.e8 * CLIGHT / lambda_min_A, time_min_days * DAY, time_max_days * DAY)
+
+
+def line_trace_request(regions, nnubins=1000, nprocs=1, abin=-1, syn_dir=(0., 0., 1.)):
+    """regions: (time_min_days, time_max_days, lambda_min_A, lambda_max_A) tuples.  The request keeps its region
+    array alive (r._regions)."""
+    r = LineTraceRequest()
+    r.nnubins, r.nprocs, r.abin, r.nregions = nnubins, nprocs, abin, len(regions)
+    for k in range(3):
+        r.syn_dir[k] = syn_dir[k]
+    r._regions = (LineTraceRegion * max(len(regions), 1))()
+    for k, reg in enumerate(regions):
+        x = r._regions[k]
+        x.nu_lower, x.nu_upper, x.time_min, x.time_max = line_trace_region(*reg)
+    r.regions = C.cast(r._regions, C.POINTER(LineTraceRegion))
+    return r
+
+
 # update_grid's temperature / ionisation solution (include/artis_gpu.h artis_te_*; ABI 7)
 TE_NRATES = 8
 TE_RATE_NAMES = ["cooling_collisional", "cooling_fb", "cooling_ff", "cooling_adiabatic", "heating_collisional",

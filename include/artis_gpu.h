@@ -563,6 +563,47 @@ typedef struct artis_spectra_res_request {
 } artis_spectra_res_request;
 int artis_gpu_spectra_res(const artis_spectra_res_request *req, artis_spectra_out *out);
 
+/* The per-line emission / absorption trace of add_to_spec (TRACE_EMISSION_ABSORPTION_REGION_ON, spectrum.cc:11-30,
+ * 395-408, 435-447, 454-468) for the resident packets: which lines emitted, and which absorbed, the flux that
+ * arrives in a wavelength and time window, and at what ejecta velocity.  The reference traces one window per run,
+ * fixed by four #defines; here up to ARTIS_LINE_TRACE_MAX_REGIONS windows are run-time arguments of one pass.
+ * Per escaped r-packet that add_to_spec admits (t_arrive inside (tmin, tmax), nu_rf inside (nu_min_r, nu_max_r), a
+ * valid timestep and frequency bin), with deltaE and deltaE_absorption exactly those of add_to_spec, and for every
+ * window with time_min <= t_arrive <= time_max and nu_lower <= nu_rf <= nu_upper (inclusive, spectrum.cc:398-399):
+ *   trueemissiontype = et >= 0:  lines[r][et][0] += deltaE, lines[r][et][1] += trueemissionvelocity * deltaE,
+ *                                totals[r][0] += deltaE;
+ *   absorptiontype = at >= 0 with absorptionfreq inside the binned band:  lines[r][at][2] += deltaE_absorption,
+ *                                lines[r][at][3] += |em_pos / em_time| * deltaE_absorption (get_velocity, vec_len),
+ *                                totals[r][1] += deltaE_absorption.
+ * abin -1: every direction with weight 1, the reference's only mode (current_abin == -1); 0 .. ARTIS_MABINS-1: only
+ * packets escaping into that direction bin about syn_dir, weighted by ARTIS_MABINS, so that the sums over an ion's
+ * lines are that ion's bound-bound trueemission / absorption columns of artis_gpu_spectra(abin).  The reference's
+ * do_emission_res gate does not apply: asking for the trace is the gate.  Results are ADDED, so the rank loop of
+ * exspec.cc:162 is one call per rank's packets with nprocs = the rank count.
+ * ARTIS_ERR_BAD_ARGUMENT (artis_gpu_last_error starts with "line_trace:"; nothing is launched, the arrays are
+ * untouched): a NULL request or output; NULL lines, totals or regions; nnubins or nprocs <= 0; abin outside
+ * [-1, ARTIS_MABINS); nregions outside [1, ARTIS_LINE_TRACE_MAX_REGIONS]; a window with a non-finite bound,
+ * nu_lower > nu_upper or time_min > time_max.  The device accumulators (the size of lines and totals) are allocated
+ * per call: when that fails the call returns ARTIS_ERR_HIP, artis_gpu_last_error states the bytes, nothing is added. */
+#define ARTIS_LINE_TRACE_MAX_REGIONS 16
+typedef struct artis_line_trace_region {
+  double nu_lower, nu_upper;  /* [Hz] 1e8 CLIGHT / lambda_max, 1e8 CLIGHT / lambda_min (spectrum.cc:15-16) */
+  double time_min, time_max;  /* [s] arrival time (spectrum.cc:17-18) */
+} artis_line_trace_region;
+typedef struct artis_line_trace_request {
+  int32_t nnubins, nprocs;    /* as artis_spectra_request */
+  int32_t abin;               /* -1 or 0 .. ARTIS_MABINS-1 */
+  int32_t nregions;
+  double syn_dir[3];
+  const artis_line_trace_region *regions;  /* [nregions] */
+} artis_line_trace_request;
+typedef struct artis_line_trace_out {
+  double *lines;   /* [nregions][nlines][4]: energyemitted, emission_weightedvelocity_sum, energyabsorbed,
+                      absorption_weightedvelocity_sum (struct emissionabsorptioncontrib, spectrum.cc:20-26) */
+  double *totals;  /* [nregions][2]: traceemission_totalenergy, traceabsorption_totalenergy */
+} artis_line_trace_out;
+int artis_gpu_line_trace(const artis_line_trace_request *req, artis_line_trace_out *out);
+
 /* --- virtual packets (VPKT_ON) ------------------------------------------------------------------------------ */
 /* Switch virtual packets on for all following updates (replaces read_parameterfile_vpkt + init_vspecpol +
  * init_vpkt_grid, vpkt.cc:408-443, 547-578, 667-835): allocates and zeroes the device accumulators.  exclude[] > 0
@@ -798,7 +839,7 @@ double artis_gpu_last_nlte_ms(void);  /* device time (ms) of the last artis_gpu_
                                    11: artis_gpu_init refuses unsupported option values; rlc_emiss_rpkt into
                                        rpkt_emiss for do_rlc_est 1 / 2; artis_gpu_table_info's level-mode entries;
                                        (still 11, an appended entry point breaks no caller) artis_gpu_spectra_res
-                                       and artis_spectra_res_request */
+                                       and artis_spectra_res_request; artis_gpu_line_trace and its structs */
 int artis_gpu_abi_version(void);
 
 #ifdef __cplusplus

@@ -120,6 +120,21 @@ int artis_write_light_curve(const char *lc_filename, int abin, int numtimesteps,
                             const double *ts_width, const double *lc_lum, const double *lc_lumcmf,
                             const double *gamma_dep, const double *cmf_lum);
 
+/* The table of the per-line emission / absorption trace (printout_tracemission_stats, spectrum.cc:58-136) for the
+ * arrays artis_gpu_line_trace fills.  The reference prints it into its log for its one region; here it is a file,
+ * emission_absorption_trace.out by convention, with one block per region: the two header lines of spectrum.cc:65-70,
+ * the column names and the emission table, a blank line, the header of spectrum.cc:73-75, the column names and the
+ * absorption table, a blank line.  A table lists the lines by descending energy (equal energies by ascending line
+ * index, which qsort leaves open), at most 500 rows, ending before the first line whose energy is not > 0.  Row
+ * format of spectrum.cc:123-127: energy (percent of the region's total), Z, ion stage, upper, lower, collision
+ * strength, A, forbidden flag, lambda [Angstrom], <v_rad> [km/s], B_lu, B_ul, with B_ul = CLIGHTSQUAREDOVERTWOH /
+ * nu_trans^3 * A from the two level energies and B_lu = g_u / g_l * B_ul.
+ * artis_rank_line_trace: the ranking alone for one region's lines[nlines][4]; column 0 (emission) or 2
+ * (absorption); writes at most maxlines line indices to ranked and returns their count, -1 for a bad argument. */
+int artis_rank_line_trace(const double *lines, int nlines, int column, int maxlines, int32_t *ranked);
+int artis_write_line_trace(const char *filename, const artis_atomic_tables *at, int nregions,
+                           const artis_line_trace_region *regions, const double *lines, const double *totals);
+
 /* The Spencer-Fano data nonthermal::init reads (nonthermal.cc:183-437) from directory dir: binding_energies.txt
  * (read_binding_energies), collion.txt (read_collion_data: the rows of the included ions -- elements anumber[e]
  * with ion stages ionstage0[e] .. ionstage0[e] + nions[e] - 1 -- in file order) and auger-km1993-table2.txt
