@@ -27,6 +27,7 @@
 #include "artis_gpu.h"
 #include "artis_rng.h"
 #include "engine_dev.h"
+#include "est_block.h"
 #include "packet_soa.h"
 #include "physics.h"
 #include "transport.h"
@@ -909,29 +910,6 @@ __global__ __launch_bounds__(TRANSPORT_BLOCK) void k_transport(const Ctx *__rest
     if (s_work[j]) atomicAdd(&K.E.work[j], s_work[j]);
 }
 
-// pack estimators into one double block (for an RCCL all-reduce by the caller) and back
-__global__ void k_pack_counts(const int32_t *ecounter, const int32_t *acounter, const unsigned long long *counters,
-                              double *dst, int nlines, int dir) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t n = 2 * (int64_t)nlines + ARTIS_COUNTER_COUNT + 1;
-  if (i >= n) return;
-  if (dir == 0) {
-    if (i < nlines)
-      dst[i] = ecounter[i];
-    else if (i < 2 * nlines)
-      dst[i] = acounter[i - nlines];
-    else
-      dst[i] = (double)counters[i - 2 * nlines];
-  } else {
-    if (i < nlines)
-      const_cast<int32_t *>(ecounter)[i] = (int32_t)llrint(dst[i]);
-    else if (i < 2 * nlines)
-      const_cast<int32_t *>(acounter)[i - nlines] = (int32_t)llrint(dst[i]);
-    else
-      const_cast<unsigned long long *>(counters)[i - 2 * nlines] = (unsigned long long)llrint(dst[i]);
-  }
-}
-
 // ================================================================================================= host side
 #include "engine_state.h"
 #include "host_tables.h"
@@ -1596,6 +1574,9 @@ int run_wavefront(int64_t n, int nts, double t2) {
 // update_grid's host drivers: artis_gpu_solve_temperatures, artis_gpu_prepare_temperatures, artis_gpu_update_grid_nlte
 #include "nlte_tables.h"
 #include "update_grid_host.h"
+// the readout side: the estimator block and its all-reduce; the spectra and the line trace
+#include "estimators_host.h"
+#include "spectra_host.h"
 
 extern "C" {
 int artis_gpu_abi_version(void) { return ARTIS_GPU_ABI_VERSION; }
@@ -1603,337 +1584,6 @@ const char *artis_gpu_last_error(void) { return G.last_error.c_str(); }
 double artis_gpu_last_transport_ms(void) { return G.last_transport_ms; }
 double artis_gpu_last_precompute_ms(void) { return G.last_precompute_ms; }
 int64_t artis_gpu_last_rounds(void) { return G.last_rounds; }
-
-// init_spectra (spectrum.cc:495-500): lower_freq and delta_freq are float arrays (spectrum.h:18-19), so the
-// bin width every deltaE divides by is the float difference of the float lower edge
-static inline double spec_delta_freq(double nu_min, double dlognu, int nnu) {
-  const float lower_freq = (float)exp(log(nu_min) + (nnu * (dlognu)));
-  return (float)(exp(log(nu_min) + ((nnu + 1) * (dlognu))) - lower_freq);
-}
-int artis_gpu_spectrum(int nnubins, int nprocs, double *spec_flux, double *lc_lum, double *lc_lumcmf) {
-  if (!G.initialised) return ARTIS_ERR_NOT_INITIALISED;
-  if (nnubins <= 0 || nprocs <= 0 || !spec_flux || !lc_lum || !lc_lumcmf) return ARTIS_ERR_BAD_ARGUMENT;
-  const int nt = G.ntstep;
-  // spectrum.cc:491-500 init_spectra: bin edges with the reference's expressions (host libm)
-  const double nu_min = G.K.G.nu_min_r, nu_max = G.K.G.nu_max_r;
-  const double dlognu = (log(nu_max) - log(nu_min)) / nnubins;
-  std::vector<double> delta(nnubins);
-  for (int nnu = 0; nnu < nnubins; nnu++)
-    delta[nnu] = spec_delta_freq(nu_min, dlognu, nnu);
-  const size_t nspec = (size_t)nt * nnubins;
-  DevBufs B;  // every step below may fail; the scratch is released (hipFree waits for the stream) on all paths
-  double *d = nullptr;
-  if (int rc = B.get(&d, nspec + 2 * (size_t)nt + nnubins, (const double *)nullptr)) return rc;
-  double *d_spec = d, *d_lc = d + nspec, *d_lccmf = d_lc + nt, *d_delta = d_lccmf + nt;
-  if (int rc = sync_ctx()) return rc;
-  HIPCHK(hipMemsetAsync(d, 0, (nspec + 2 * (size_t)nt) * sizeof(double), G.stream));
-  HIPCHK(hipMemcpyAsync(d_delta, delta.data(), nnubins * sizeof(double), hipMemcpyHostToDevice, G.stream));
-  if (G.npkts > 0)
-    k_spectrum<<<(unsigned)((G.npkts + 255) / 256), 256, 0, G.stream>>>(
-        G.d_ctx, G.d_soa, G.npkts, nt, nnubins, dlognu, d_delta, (double)nprocs, d_spec, d_lc, d_lccmf);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(spec_flux, d_spec, nspec * sizeof(double), hipMemcpyDeviceToHost, G.stream));
-  HIPCHK(hipMemcpyAsync(lc_lum, d_lc, nt * sizeof(double), hipMemcpyDeviceToHost, G.stream));
-  HIPCHK(hipMemcpyAsync(lc_lumcmf, d_lccmf, nt * sizeof(double), hipMemcpyDeviceToHost, G.stream));
-  HIPCHK(hipStreamSynchronize(G.stream));
-  return 0;
-}
-int artis_gpu_spectra(const artis_spectra_request *req, artis_spectra_out *out) {
-  if (!G.initialised) return ARTIS_ERR_NOT_INITIALISED;
-  if (!req || !out || req->nnubins <= 0 || req->nprocs <= 0 || req->abin < -1 || req->abin >= ARTIS_MABINS ||
-      (!out->emission != !out->absorption) || (out->trueemission && !out->emission) ||
-      ((out->stokes_emission || out->stokes_absorption) && !out->emission)) {
-    G.last_error = "spectra: bad request (nnubins, nprocs, abin) or inconsistent emission/absorption arrays";
-    return ARTIS_ERR_BAD_ARGUMENT;
-  }
-  const int nt = G.ntstep, nnb = req->nnubins;
-  const int ioncount = G.nelements * G.maxnions, proccount = 2 * ioncount + 1;
-  const double nu_min = G.K.G.nu_min_r, nu_max = G.K.G.nu_max_r;
-  const double dlognu = (log(nu_max) - log(nu_min)) / nnb;  // spectrum.cc:352, 491-500 (host libm)
-  std::vector<double> delta(nnb);
-  for (int nnu = 0; nnu < nnb; nnu++)
-    delta[nnu] = spec_delta_freq(nu_min, dlognu, nnu);
-  const size_t nb = (size_t)nt * nnb;
-  // device accumulators, in the order of the sections below
-  struct Sec {
-    double *host;
-    size_t n;
-  } secs[] = {{out->flux, nb},
-              {out->emission, nb * proccount},
-              {out->trueemission, nb * proccount},
-              {out->absorption, nb * ioncount},
-              {out->stokes_flux, 3 * nb},
-              {out->stokes_emission, 3 * nb * proccount},
-              {out->stokes_absorption, 3 * nb * ioncount},
-              {out->lc_lum, (size_t)nt},
-              {out->lc_lumcmf, (size_t)nt},
-              {out->gamma_lc_lum, (size_t)nt},
-              {out->gamma_lc_lumcmf, (size_t)nt}};
-  constexpr int NSEC = sizeof(secs) / sizeof(secs[0]);
-  size_t total = nnb;  // delta_freq first
-  for (const Sec &x : secs)
-    if (x.host) total += x.n;
-  DevBufs B;  // released on every path
-  double *d = nullptr;
-  if (int rc = B.get(&d, total, (const double *)nullptr)) return rc;
-  double *dptr[NSEC];
-  size_t off = nnb;
-  for (int k = 0; k < NSEC; k++) {
-    dptr[k] = secs[k].host ? d + off : nullptr;
-    if (secs[k].host) off += secs[k].n;
-  }
-  if (int rc = sync_ctx()) return rc;
-  HIPCHK(hipMemsetAsync(d + nnb, 0, (total - nnb) * sizeof(double), G.stream));
-  HIPCHK(hipMemcpyAsync(d, delta.data(), nnb * sizeof(double), hipMemcpyHostToDevice, G.stream));
-  SpecArgs A{};
-  A.nnubins = nnb;
-  A.nprocs = req->nprocs;
-  A.abin = req->abin;
-  A.ntstep = nt;
-  A.proccount = proccount;
-  A.ioncount = ioncount;
-  A.maxnions = G.maxnions;
-  A.nbf = G.K.T.nbf;
-  for (int k = 0; k < 3; k++) A.syn_dir[k] = req->syn_dir[k];
-  A.dlognu = dlognu;
-  A.delta_freq = d;
-  A.bf_col = G.d_bfcol;
-  A.line_elem = G.K.T.line_elem;
-  A.line_ion = G.K.T.line_ion;
-  A.flux = dptr[0];
-  A.emission = dptr[1];
-  A.trueemission = dptr[2];
-  A.absorption = dptr[3];
-  A.sflux = dptr[4];
-  A.semission = dptr[5];
-  A.sabsorption = dptr[6];
-  A.lc = dptr[7];
-  A.lccmf = dptr[8];
-  A.glc = dptr[9];
-  A.glccmf = dptr[10];
-  if (G.npkts > 0)
-    k_spectra<<<(unsigned)((G.npkts + 255) / 256), 256, 0, G.stream>>>(G.d_ctx, G.d_soa, G.npkts, A);
-  HIPCHK(hipGetLastError());
-  std::vector<double> h;
-  for (int k = 0; k < NSEC; k++) {
-    if (!secs[k].host) continue;
-    h.resize(secs[k].n);
-    HIPCHK(hipMemcpyAsync(h.data(), dptr[k], secs[k].n * sizeof(double), hipMemcpyDeviceToHost, G.stream));
-    HIPCHK(hipStreamSynchronize(G.stream));
-    for (size_t j = 0; j < secs[k].n; j++) secs[k].host[j] += h[j];
-  }
-  return 0;
-}
-
-// The direction-resolved set in one pass (k_spectra_res): slot 0 the angle average (with_average), then the bins
-// [abin_first, abin_first + abin_count); every spectrum array and lc_lum carry the leading slot dimension.
-int artis_gpu_spectra_res(const artis_spectra_res_request *req, artis_spectra_out *out) {
-  if (!G.initialised) return ARTIS_ERR_NOT_INITIALISED;
-  if (!req || !out) {
-    G.last_error = "spectra_res: NULL request or output";
-    return ARTIS_ERR_BAD_ARGUMENT;
-  }
-  if (req->nnubins <= 0 || req->nprocs <= 0 || req->abin_first < 0 || req->abin_count < 0 ||
-      req->abin_first > ARTIS_MABINS || req->abin_count > ARTIS_MABINS - req->abin_first ||
-      (req->with_average != 0 && req->with_average != 1) || (req->abin_count == 0 && !req->with_average)) {
-    G.last_error = "spectra_res: bad request (nnubins, nprocs > 0; bins [abin_first, abin_first + abin_count) within "
-                   "[0, ARTIS_MABINS]; with_average 0 or 1; no bins needs with_average)";
-    return ARTIS_ERR_BAD_ARGUMENT;
-  }
-  if ((!out->emission != !out->absorption) || (out->trueemission && !out->emission) ||
-      ((out->stokes_emission || out->stokes_absorption) && !out->emission)) {
-    G.last_error = "spectra_res: inconsistent emission / absorption / Stokes arrays";
-    return ARTIS_ERR_BAD_ARGUMENT;
-  }
-  if (!req->with_average && (out->lc_lumcmf || out->gamma_lc_lum || out->gamma_lc_lumcmf)) {
-    G.last_error = "spectra_res: lc_lumcmf and the gamma-ray light curves belong to the angle average: NULL without "
-                   "with_average";
-    return ARTIS_ERR_BAD_ARGUMENT;
-  }
-  const int nt = G.ntstep, nnb = req->nnubins;
-  const int ioncount = G.nelements * G.maxnions, proccount = 2 * ioncount + 1;
-  const size_t nslots = (size_t)req->with_average + (size_t)req->abin_count;
-  const double nu_min = G.K.G.nu_min_r, nu_max = G.K.G.nu_max_r;
-  const double dlognu = (log(nu_max) - log(nu_min)) / nnb;  // spectrum.cc:352, 491-500 (host libm)
-  std::vector<double> delta(nnb);
-  for (int nnu = 0; nnu < nnb; nnu++)
-    delta[nnu] = spec_delta_freq(nu_min, dlognu, nnu);
-  const size_t nb = (size_t)nt * nnb;
-  // device accumulators, in the order of the sections below
-  struct Sec {
-    double *host;
-    size_t n;
-  } secs[] = {{out->flux, nslots * nb},
-              {out->emission, nslots * nb * proccount},
-              {out->trueemission, nslots * nb * proccount},
-              {out->absorption, nslots * nb * ioncount},
-              {out->stokes_flux, nslots * 3 * nb},
-              {out->stokes_emission, nslots * 3 * nb * proccount},
-              {out->stokes_absorption, nslots * 3 * nb * ioncount},
-              {out->lc_lum, nslots * nt},
-              {out->lc_lumcmf, (size_t)nt},
-              {out->gamma_lc_lum, (size_t)nt},
-              {out->gamma_lc_lumcmf, (size_t)nt}};
-  constexpr int NSEC = sizeof(secs) / sizeof(secs[0]);
-  size_t total = nnb;  // delta_freq first
-  for (const Sec &x : secs)
-    if (x.host) total += x.n;
-  {
-    // all slots or none: a request that does not fit is refused before anything is allocated or binned
-    size_t freeb = 0, totalb = 0;
-    HIPCHK(hipMemGetInfo(&freeb, &totalb));
-    if (total * sizeof(double) > freeb) {
-      G.last_error = "spectra_res: out of device memory: the accumulators of " + std::to_string(nslots) +
-                     " slots need " + std::to_string(total * sizeof(double)) + " bytes, " + std::to_string(freeb) +
-                     " are free; ask for fewer direction bins per call (a smaller abin_count)";
-      return ARTIS_ERR_HIP;
-    }
-  }
-  DevBufs B;  // released on every path
-  double *d = nullptr;
-  if (int rc = B.get(&d, total, (const double *)nullptr)) {
-    (void)hipGetLastError();  // the failed allocation is reported here, not by the next launch check
-    G.last_error = "spectra_res: out of device memory: allocating " + std::to_string(total * sizeof(double)) +
-                   " bytes of accumulators failed; ask for fewer direction bins per call (a smaller abin_count)";
-    return rc;
-  }
-  double *dptr[NSEC];
-  size_t off = nnb;
-  for (int k = 0; k < NSEC; k++) {
-    dptr[k] = secs[k].host ? d + off : nullptr;
-    if (secs[k].host) off += secs[k].n;
-  }
-  if (int rc = sync_ctx()) return rc;
-  HIPCHK(hipMemsetAsync(d + nnb, 0, (total - nnb) * sizeof(double), G.stream));
-  HIPCHK(hipMemcpyAsync(d, delta.data(), nnb * sizeof(double), hipMemcpyHostToDevice, G.stream));
-  SpecArgs A{};
-  A.nnubins = nnb;
-  A.nprocs = req->nprocs;
-  A.abin = -1;
-  A.ntstep = nt;
-  A.proccount = proccount;
-  A.ioncount = ioncount;
-  A.maxnions = G.maxnions;
-  A.nbf = G.K.T.nbf;
-  for (int k = 0; k < 3; k++) A.syn_dir[k] = req->syn_dir[k];
-  A.dlognu = dlognu;
-  A.delta_freq = d;
-  A.bf_col = G.d_bfcol;
-  A.line_elem = G.K.T.line_elem;
-  A.line_ion = G.K.T.line_ion;
-  A.flux = dptr[0];
-  A.emission = dptr[1];
-  A.trueemission = dptr[2];
-  A.absorption = dptr[3];
-  A.sflux = dptr[4];
-  A.semission = dptr[5];
-  A.sabsorption = dptr[6];
-  A.lc = dptr[7];
-  A.lccmf = dptr[8];
-  A.glc = dptr[9];
-  A.glccmf = dptr[10];
-  const SpecResArgs R{req->abin_first, req->abin_count, req->with_average};
-  if (G.npkts > 0)
-    k_spectra_res<<<(unsigned)((G.npkts + 255) / 256), 256, 0, G.stream>>>(G.d_ctx, G.d_soa, G.npkts, A, R);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(G.stream));  // a kernel fault is reported before anything is added to the caller's arrays
-  // copy back through a bounded staging buffer and ADD
-  std::vector<double> h;
-  constexpr size_t STAGE = (size_t)8 << 20;  // doubles (64 MiB)
-  for (int k = 0; k < NSEC; k++) {
-    if (!secs[k].host) continue;
-    for (size_t o = 0; o < secs[k].n; o += STAGE) {
-      const size_t m = std::min(STAGE, secs[k].n - o);
-      h.resize(m);
-      HIPCHK(hipMemcpyAsync(h.data(), dptr[k] + o, m * sizeof(double), hipMemcpyDeviceToHost, G.stream));
-      HIPCHK(hipStreamSynchronize(G.stream));
-      double *dst = secs[k].host + o;
-      for (size_t j = 0; j < m; j++) dst[j] += h[j];
-    }
-  }
-  return 0;
-}
-
-// The per-line emission / absorption trace (k_line_trace): lines [nregions][nlines][4] and totals [nregions][2],
-// accumulated on the device per call and ADDED into the caller's arrays.
-int artis_gpu_line_trace(const artis_line_trace_request *req, artis_line_trace_out *out) {
-  if (!G.initialised) return ARTIS_ERR_NOT_INITIALISED;
-  if (!req || !out) {
-    G.last_error = "line_trace: NULL request or output";
-    return ARTIS_ERR_BAD_ARGUMENT;
-  }
-  if (!out->lines || !out->totals || !req->regions) {
-    G.last_error = "line_trace: NULL lines, totals or regions";
-    return ARTIS_ERR_BAD_ARGUMENT;
-  }
-  if (req->nnubins <= 0 || req->nprocs <= 0 || req->abin < -1 || req->abin >= ARTIS_MABINS || req->nregions < 1 ||
-      req->nregions > ARTIS_LINE_TRACE_MAX_REGIONS) {
-    G.last_error = "line_trace: bad request (nnubins, nprocs > 0; abin in [-1, ARTIS_MABINS); nregions in "
-                   "[1, ARTIS_LINE_TRACE_MAX_REGIONS])";
-    return ARTIS_ERR_BAD_ARGUMENT;
-  }
-  for (int r = 0; r < req->nregions; r++) {
-    const artis_line_trace_region &R = req->regions[r];
-    if (!std::isfinite(R.nu_lower) || !std::isfinite(R.nu_upper) || !std::isfinite(R.time_min) ||
-        !std::isfinite(R.time_max) || R.nu_lower > R.nu_upper || R.time_min > R.time_max) {
-      G.last_error = "line_trace: region " + std::to_string(r) +
-                     " has a non-finite bound, nu_lower > nu_upper or time_min > time_max";
-      return ARTIS_ERR_BAD_ARGUMENT;
-    }
-  }
-  const int nnb = req->nnubins, nreg = req->nregions;
-  const double nu_min = G.K.G.nu_min_r, nu_max = G.K.G.nu_max_r;
-  const double dlognu = (log(nu_max) - log(nu_min)) / nnb;  // spectrum.cc:352, 491-500 (host libm)
-  std::vector<double> delta(nnb);
-  for (int nnu = 0; nnu < nnb; nnu++)
-    delta[nnu] = spec_delta_freq(nu_min, dlognu, nnu);
-  const size_t nlin = (size_t)nreg * G.nlines * 4, ntot = (size_t)nreg * 2;
-  const size_t total = nnb + nlin + ntot;  // delta_freq first, then lines, then totals
-  DevBufs B;  // released on every path
-  double *d = nullptr;
-  if (int rc = B.get(&d, total, (const double *)nullptr)) {
-    (void)hipGetLastError();  // the failed allocation is reported here, not by the next launch check
-    G.last_error = "line_trace: out of device memory: allocating " + std::to_string(total * sizeof(double)) +
-                   " bytes of accumulators failed; ask for fewer regions per call";
-    return rc;
-  }
-  if (int rc = sync_ctx()) return rc;
-  HIPCHK(hipMemsetAsync(d + nnb, 0, (nlin + ntot) * sizeof(double), G.stream));
-  HIPCHK(hipMemcpyAsync(d, delta.data(), nnb * sizeof(double), hipMemcpyHostToDevice, G.stream));
-  LineTraceArgs A{};
-  A.nnubins = nnb;
-  A.nprocs = req->nprocs;
-  A.abin = req->abin;
-  A.ntstep = G.ntstep;
-  A.nregions = nreg;
-  A.nlines = G.nlines;
-  for (int k = 0; k < 3; k++) A.syn_dir[k] = req->syn_dir[k];
-  A.dlognu = dlognu;
-  A.delta_freq = d;
-  A.lines = d + nnb;
-  A.totals = d + nnb + nlin;
-  for (int r = 0; r < nreg; r++) A.regions[r] = req->regions[r];
-  if (G.npkts > 0)
-    k_line_trace<<<(unsigned)((G.npkts + 255) / 256), 256, 0, G.stream>>>(G.d_ctx, G.d_soa, G.npkts, A);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(G.stream));  // a kernel fault is reported before anything is added to the caller's arrays
-  // copy back through a small staging buffer that stays warm, and ADD (lines and totals are contiguous on the device)
-  constexpr size_t STAGE = (size_t)1 << 19;  // doubles (4 MiB)
-  std::vector<double> h(std::min(STAGE, nlin + ntot));
-  for (size_t o = 0; o < nlin + ntot; o += STAGE) {
-    const size_t m = std::min(STAGE, nlin + ntot - o);
-    HIPCHK(hipMemcpyAsync(h.data(), d + nnb + o, m * sizeof(double), hipMemcpyDeviceToHost, G.stream));
-    HIPCHK(hipStreamSynchronize(G.stream));
-    for (size_t j = 0; j < m; j++) {
-      const size_t g = o + j;
-      if (g < nlin)
-        out->lines[g] += h[j];
-      else
-        out->totals[g - nlin] += h[j];
-    }
-  }
-  return 0;
-}
 
 int artis_gpu_vpkt_init(const artis_vpkt_params *vp) {
   if (!G.initialised) return ARTIS_ERR_NOT_INITIALISED;
@@ -2460,11 +2110,8 @@ static void set_run_params(const artis_run_params *rp) {
 // the estimator block and the event counters
 static int lay_out_estimators_on_device(const artis_atomic_tables *a, const artis_geometry *g,
                                         const artis_run_params *rp) {
-  const EstLayout L = lay_out_estimators(a, g, rp);
-  G.nbf_est = L.nbf_est;
-  G.nbins_est = L.nbins_est;
-  G.n_est_doubles = L.n_doubles;
-  if (dalloc(&G.d_estblock, G.n_est_doubles)) return ARTIS_ERR_HIP;
+  const EstLayout &L = G.est = lay_out_estimators(a, g, rp);
+  if (dalloc(&G.d_estblock, L.n_doubles)) return ARTIS_ERR_HIP;
   int rc = 0;
   DevEst &E = G.K.E;
   E.J = G.d_estblock + L.J;
@@ -2482,7 +2129,7 @@ static int lay_out_estimators_on_device(const artis_atomic_tables *a, const arti
   E.compton = G.d_estblock + L.compton;
   rc |= dalloc(&E.ecounter, a->nlines);
   rc |= dalloc(&E.acounter, a->nlines);
-  rc |= dalloc(&E.counters, ARTIS_COUNTER_COUNT + 1);
+  rc |= dalloc(&E.counters, ARTIS_COUNTER_COUNT + 1);  // the counters, then nesc
   rc |= dalloc(&E.work, ARTIS_WORK_COUNT);
   rc |= dalloc(&E.err, 4);
   return rc ? ARTIS_ERR_HIP : 0;
@@ -2966,16 +2613,6 @@ int artis_gpu_packets_restore(void) {
   return 0;
 }
 
-int artis_gpu_estimators_zero(void) {
-  if (!G.initialised) return ARTIS_ERR_NOT_INITIALISED;
-  const DevEst &E = G.K.E;
-  HIPCHK(hipMemsetAsync(G.d_estblock, 0, (size_t)G.n_est_doubles * sizeof(double), G.stream));
-  HIPCHK(hipMemsetAsync(E.ecounter, 0, (size_t)G.nlines * sizeof(int32_t), G.stream));
-  HIPCHK(hipMemsetAsync(E.acounter, 0, (size_t)G.nlines * sizeof(int32_t), G.stream));
-  HIPCHK(hipMemsetAsync(E.counters, 0, (ARTIS_COUNTER_COUNT + 1) * sizeof(unsigned long long), G.stream));
-  return 0;
-}
-
 int artis_gpu_update_packets_resident(int my_rank, int nts) {
   if (!G.initialised) return ARTIS_ERR_NOT_INITIALISED;
   if (!G.have_cells || G.cellstate_nts != nts) {
@@ -3042,250 +2679,6 @@ int artis_gpu_update_packets_resident(int my_rank, int nts) {
     G.ma_acts_cached = (int64_t)w[WK_MA_JUMPS] - (int64_t)coop;
   }
   return check_kernel_error("update_packets");
-}
-
-int artis_gpu_estimators_download(artis_estimators *est) {
-  if (!G.initialised) return ARTIS_ERR_NOT_INITIALISED;
-  if (!est) return ARTIS_ERR_BAD_ARGUMENT;
-  HIPCHK(hipStreamSynchronize(G.stream));
-  const int np = G.npts_model;
-  const int64_t nion_est = (int64_t)np * G.nelements * G.maxnions;
-  std::vector<double> blk(G.n_est_doubles);
-  HIPCHK(hipMemcpy(blk.data(), G.d_estblock, blk.size() * sizeof(double), hipMemcpyDeviceToHost));
-  auto add = [&](double *dst, int64_t off, int64_t cnt) {
-    if (!dst) return;
-    for (int64_t j = 0; j < cnt; j++) dst[j] += blk[off + j];
-  };
-  add(est->J, 0, np);
-  add(est->nuJ, np, np);
-  add(est->ffheatingestimator, 2 * (int64_t)np, np);
-  add(est->colheatingestimator, 3 * (int64_t)np, np);
-  add(est->rpkt_emiss, 4 * (int64_t)np, np);
-  add(est->gammaestimator, 5 * (int64_t)np, nion_est);
-  add(est->bfheatingestimator, 5 * (int64_t)np + nion_est, nion_est);
-  const double *sc = blk.data() + 5 * (int64_t)np + 2 * nion_est;
-  est->cmf_lum += sc[0];
-  est->gamma_dep += sc[1];
-  est->positron_dep += sc[2];
-  est->electron_dep += sc[3];
-  est->electron_emission += sc[4];
-  est->alpha_dep += sc[5];
-  est->alpha_emission += sc[6];
-  est->gamma_emission += sc[7];
-  est->nt_energy_deposited += sc[8];
-  est->pellet_decays += (int64_t)llrint(sc[9]);
-  const int64_t off_bf = 5 * (int64_t)np + 2 * nion_est + 10;
-  if (G.nbf_est) add(est->bfrate_raw, off_bf, (int64_t)np * G.nbf_est);
-  if (G.nbins_est) {
-    const int64_t nbn = (int64_t)np * G.nbins_est, off_rf = off_bf + (int64_t)np * G.nbf_est;
-    add(est->radfield_J_raw, off_rf, nbn);
-    add(est->radfield_nuJ_raw, off_rf + nbn, nbn);
-    if (est->radfield_contribcount)
-      for (int64_t j = 0; j < nbn; j++) est->radfield_contribcount[j] += (int64_t)llrint(blk[off_rf + 2 * nbn + j]);
-  }
-  if (est->compton_emiss) {  // the double sums added to the caller's float array (globals::compton_emiss)
-    const int64_t off_ce = off_bf + (int64_t)np * (G.nbf_est + 3 * G.nbins_est);
-    for (int64_t j = 0; j < ((int64_t)np + 1) * ARTIS_EMISS_MAX; j++)
-      est->compton_emiss[j] = (float)((double)est->compton_emiss[j] + blk[off_ce + j]);
-  }
-  std::vector<int32_t> lc(G.nlines);
-  if (est->ecounter) {
-    HIPCHK(hipMemcpy(lc.data(), G.K.E.ecounter, lc.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (int j = 0; j < G.nlines; j++) est->ecounter[j] += lc[j];
-  }
-  if (est->acounter) {
-    HIPCHK(hipMemcpy(lc.data(), G.K.E.acounter, lc.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (int j = 0; j < G.nlines; j++) est->acounter[j] += lc[j];
-  }
-  unsigned long long ctr[ARTIS_COUNTER_COUNT + 1];
-  HIPCHK(hipMemcpy(ctr, G.K.E.counters, sizeof(ctr), hipMemcpyDeviceToHost));
-  for (int j = 0; j < ARTIS_COUNTER_COUNT; j++) est->counters[j] += (int64_t)ctr[j];
-  est->nesc += (int64_t)ctr[ARTIS_COUNTER_COUNT];
-  return 0;
-}
-
-size_t artis_gpu_estimator_block_doubles(void) {
-  if (!G.initialised) return 0;
-  return (size_t)G.n_est_doubles + 2 * (size_t)G.nlines + ARTIS_COUNTER_COUNT + 1;
-}
-
-int artis_gpu_estimator_block_to_device(void *dst) {
-  if (!G.initialised) return ARTIS_ERR_NOT_INITIALISED;
-  double *d = (double *)dst;
-  HIPCHK(hipMemcpyAsync(d, G.d_estblock, (size_t)G.n_est_doubles * sizeof(double), hipMemcpyDeviceToDevice, G.stream));
-  const int64_t nc = 2 * (int64_t)G.nlines + ARTIS_COUNTER_COUNT + 1;
-  k_pack_counts<<<(unsigned)((nc + 255) / 256), 256, 0, G.stream>>>(G.K.E.ecounter, G.K.E.acounter, G.K.E.counters,
-                                                                     d + G.n_est_doubles, G.nlines, 0);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(G.stream));
-  return 0;
-}
-
-int artis_gpu_estimator_block_from_device(const void *src) {
-  if (!G.initialised) return ARTIS_ERR_NOT_INITIALISED;
-  const double *s = (const double *)src;
-  HIPCHK(hipMemcpyAsync(G.d_estblock, s, (size_t)G.n_est_doubles * sizeof(double), hipMemcpyDeviceToDevice, G.stream));
-  const int64_t nc = 2 * (int64_t)G.nlines + ARTIS_COUNTER_COUNT + 1;
-  k_pack_counts<<<(unsigned)((nc + 255) / 256), 256, 0, G.stream>>>(G.K.E.ecounter, G.K.E.acounter, G.K.E.counters,
-                                                                     const_cast<double *>(s) + G.n_est_doubles,
-                                                                     G.nlines, 1);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(G.stream));
-  return 0;
-}
-
-// host mirror of the device block (artis_gpu_estimator_block_to_device / estimators_download)
-size_t artis_estimator_block_len(int np, int ne, int mi, int nl, int nbf, int nbins) {
-  if (np < 0 || ne < 0 || mi < 0 || nl < 0 || nbf < 0 || nbins < 0) return 0;
-  return 5 * (size_t)np + 2 * (size_t)np * ne * mi + 10 + (size_t)np * (nbf + 3 * (size_t)nbins) +
-         ((size_t)np + 1) * ARTIS_EMISS_MAX + 2 * (size_t)nl + ARTIS_COUNTER_COUNT + 1;
-}
-
-int artis_estimator_block_pack(const artis_estimators *est, int np, int ne, int mi, int nl, int nbf, int nbins,
-                               double *b) {
-  if (!est || !b || np < 0 || ne < 0 || mi < 0 || nl < 0 || nbf < 0 || nbins < 0) return ARTIS_ERR_BAD_ARGUMENT;
-  const size_t ni = (size_t)np * ne * mi;
-  auto put = [&](const double *src, size_t n) {
-    for (size_t j = 0; j < n; j++) *b++ = src ? src[j] : 0.;
-  };
-  put(est->J, np);
-  put(est->nuJ, np);
-  put(est->ffheatingestimator, np);
-  put(est->colheatingestimator, np);
-  put(est->rpkt_emiss, np);
-  put(est->gammaestimator, ni);
-  put(est->bfheatingestimator, ni);
-  const double sc[10] = {est->cmf_lum,        est->gamma_dep,   est->positron_dep,        est->electron_dep,
-                         est->electron_emission, est->alpha_dep, est->alpha_emission,     est->gamma_emission,
-                         est->nt_energy_deposited, (double)est->pellet_decays};
-  put(sc, 10);
-  put(est->bfrate_raw, (size_t)np * nbf);
-  put(est->radfield_J_raw, (size_t)np * nbins);
-  put(est->radfield_nuJ_raw, (size_t)np * nbins);
-  for (size_t j = 0; j < (size_t)np * nbins; j++)
-    *b++ = est->radfield_contribcount ? (double)est->radfield_contribcount[j] : 0.;
-  for (size_t j = 0; j < ((size_t)np + 1) * ARTIS_EMISS_MAX; j++)
-    *b++ = est->compton_emiss ? (double)est->compton_emiss[j] : 0.;
-  for (int j = 0; j < nl; j++) *b++ = est->ecounter ? est->ecounter[j] : 0.;
-  for (int j = 0; j < nl; j++) *b++ = est->acounter ? est->acounter[j] : 0.;
-  for (int j = 0; j < ARTIS_COUNTER_COUNT; j++) *b++ = (double)est->counters[j];
-  *b++ = (double)est->nesc;
-  return 0;
-}
-
-int artis_estimator_block_average_scalars(double *b, int np, int ne, int mi, int nranks) {
-  if (!b || np < 0 || ne < 0 || mi < 0 || nranks <= 0) return ARTIS_ERR_BAD_ARGUMENT;
-  double *sc = b + 5 * (size_t)np + 2 * (size_t)np * ne * mi;
-  for (int j = 0; j < 8; j++) sc[j] /= nranks;  // sn3d.cc:370-377
-  return 0;
-}
-
-int artis_estimator_block_unpack(const double *b, int np, int ne, int mi, int nl, int nbf, int nbins,
-                                 artis_estimators *est) {
-  if (!est || !b || np < 0 || ne < 0 || mi < 0 || nl < 0 || nbf < 0 || nbins < 0) return ARTIS_ERR_BAD_ARGUMENT;
-  const size_t ni = (size_t)np * ne * mi;
-  auto get = [&](double *dst, size_t n) {
-    if (dst)
-      for (size_t j = 0; j < n; j++) dst[j] = b[j];
-    b += n;
-  };
-  get(est->J, np);
-  get(est->nuJ, np);
-  get(est->ffheatingestimator, np);
-  get(est->colheatingestimator, np);
-  get(est->rpkt_emiss, np);
-  get(est->gammaestimator, ni);
-  get(est->bfheatingestimator, ni);
-  est->cmf_lum = b[0];
-  est->gamma_dep = b[1];
-  est->positron_dep = b[2];
-  est->electron_dep = b[3];
-  est->electron_emission = b[4];
-  est->alpha_dep = b[5];
-  est->alpha_emission = b[6];
-  est->gamma_emission = b[7];
-  est->nt_energy_deposited = b[8];
-  est->pellet_decays = (int64_t)llrint(b[9]);
-  b += 10;
-  get(est->bfrate_raw, (size_t)np * nbf);
-  get(est->radfield_J_raw, (size_t)np * nbins);
-  get(est->radfield_nuJ_raw, (size_t)np * nbins);
-  for (size_t j = 0; j < (size_t)np * nbins; j++)
-    if (est->radfield_contribcount) est->radfield_contribcount[j] = (int64_t)llrint(b[j]);
-  b += (size_t)np * nbins;
-  for (size_t j = 0; j < ((size_t)np + 1) * ARTIS_EMISS_MAX; j++)
-    if (est->compton_emiss) est->compton_emiss[j] = (float)b[j];
-  b += ((size_t)np + 1) * ARTIS_EMISS_MAX;
-  for (int j = 0; j < nl; j++)
-    if (est->ecounter) est->ecounter[j] = (int32_t)llrint(b[j]);
-  b += nl;
-  for (int j = 0; j < nl; j++)
-    if (est->acounter) est->acounter[j] = (int32_t)llrint(b[j]);
-  b += nl;
-  for (int j = 0; j < ARTIS_COUNTER_COUNT; j++) est->counters[j] = (int64_t)llrint(b[j]);
-  est->nesc = (int64_t)llrint(b[ARTIS_COUNTER_COUNT]);
-  return 0;
-}
-
-#define NCCLCHK(x)                                                                            \
-  do {                                                                                        \
-    ncclResult_t r_ = (x);                                                                    \
-    if (r_ != ncclSuccess) {                                                                  \
-      G.last_error = std::string(#x) + ": " + ncclGetErrorString(r_);                         \
-      return ARTIS_ERR_HIP;                                                                   \
-    }                                                                                         \
-  } while (0)
-
-int artis_gpu_comm_unique_id(void *id) {
-  if (!id) return ARTIS_ERR_BAD_ARGUMENT;
-  static_assert(sizeof(ncclUniqueId) == ARTIS_COMM_ID_BYTES, "RCCL unique id size");
-  ncclUniqueId uid;
-  NCCLCHK(ncclGetUniqueId(&uid));
-  memcpy(id, &uid, sizeof uid);
-  return 0;
-}
-
-int artis_gpu_comm_init(int rank, int nranks, const void *id) {
-  if (!G.initialised) return ARTIS_ERR_NOT_INITIALISED;
-  if (!id || nranks <= 0 || rank < 0 || rank >= nranks) return ARTIS_ERR_BAD_ARGUMENT;
-  artis_gpu_comm_finalize();
-  HIPCHK(hipSetDevice(G.device));
-  ncclUniqueId uid;
-  memcpy(&uid, id, sizeof uid);
-  NCCLCHK(ncclCommInitRank(&G.comm, nranks, uid, rank));
-  G.comm_ranks = nranks;
-  if (!G.d_redblock) HIPCHK(dmalloc((void **)&G.d_redblock, artis_gpu_estimator_block_doubles() * sizeof(double)));
-  return 0;
-}
-
-// mpi_reduce_estimators divides the eight time_step scalars by nprocs after the sum (sn3d.cc:370-377): every rank
-// carries a full-energy ensemble.  The arrays stay sums (update_grid divides them by nprocs, update_grid.cc:1041).
-__global__ void k_average_timestep_scalars(double *sc, int nranks) {
-  if (threadIdx.x < 8) sc[threadIdx.x] /= nranks;
-}
-
-int artis_gpu_estimators_allreduce(void) {
-  if (!G.initialised) return ARTIS_ERR_NOT_INITIALISED;
-  if (!G.comm || !G.d_redblock) {
-    G.last_error = "artis_gpu_comm_init must precede artis_gpu_estimators_allreduce";
-    return ARTIS_ERR_BAD_ARGUMENT;
-  }
-  if (int rc = artis_gpu_estimator_block_to_device(G.d_redblock)) return rc;
-  NCCLCHK(ncclAllReduce(G.d_redblock, G.d_redblock, artis_gpu_estimator_block_doubles(), ncclFloat64, ncclSum, G.comm,
-                        G.stream));
-  const int64_t off_sc = 5 * (int64_t)G.npts_model + 2 * (int64_t)G.npts_model * G.nelements * G.maxnions;
-  k_average_timestep_scalars<<<1, 64, 0, G.stream>>>(G.d_redblock + off_sc, G.comm_ranks);
-  HIPCHK(hipGetLastError());
-  return artis_gpu_estimator_block_from_device(G.d_redblock);
-}
-
-void artis_gpu_comm_finalize(void) {
-  if (G.comm) {
-    (void)hipStreamSynchronize(G.stream);
-    (void)ncclCommDestroy(G.comm);
-  }
-  G.comm = nullptr;
-  G.comm_ranks = 0;
 }
 
 int artis_gpu_update_packets(int my_rank, int nts, artis_packet *packets, int npkts, artis_estimators *est) {

@@ -1,7 +1,8 @@
 // engine_state.h -- the host state of the engine: environment knobs, the owners of device memory, the Engine
 // singleton, HIPCHK and the call-scoped DevBufs / CallerArrays.  Host code only; included once by engine.hip, after
-// its kernels (Ctx, WaveState, QagWs and the MA_BUILD_SMALL / VPKT_OCC_DEFAULT constants come from there) and before
-// host_tables.h, nlte_tables.h and update_grid_host.h.
+// its kernels (Ctx, WaveState, QagWs and the MA_BUILD_SMALL / VPKT_OCC_DEFAULT constants come from there) and
+// est_block.h (EstLayout), and before host_tables.h, nlte_tables.h and the host drivers update_grid_host.h,
+// estimators_host.h and spectra_host.h.
 #pragma once
 
 namespace {
@@ -219,7 +220,7 @@ struct Engine {
   artis_run_params params{};
   // sizes
   int npts_model = 0, nelements = 0, maxnions = 0, nions_total = 0, nlines = 0, ngrid = 0, ntstep = 0;
-  int64_t n_est_doubles = 0;  // J..bfheat + scalars
+  EstLayout est{};  // the estimator block as laid out at init (est_block.h)
   int64_t ma_key_stride = 0;          // 16-bit keys per cell block of the macro-atom cache
   bool ma_cache_ok = true;             // the atomic data fit the cache's record layout (engine_dev.h ma_layout)
   std::vector<int64_t> h_dbl_off;     // per level: offset (doubles) of its exact sums in the k_marates scratch
@@ -260,7 +261,6 @@ struct Engine {
   QagWs qag{};
   int32_t *d_bfcol = nullptr;  // bflist index -> element * maxnions + ion (spectra emission columns)
   int qag_waves = 0;
-  int64_t nbf_est = 0, nbins_est = 0;  // nebular estimator sections of the block (0 when off)
   int32_t *d_ne_index = nullptr, *d_ne_mgi = nullptr;
   // packets
   uint64_t *d_soa = nullptr, *d_aos = nullptr, *d_snapshot = nullptr;

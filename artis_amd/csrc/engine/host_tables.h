@@ -2,7 +2,8 @@
 // them.  Pure host functions: no HIP call, no engine state.  Their expressions are the reference's, operand for
 // operand (host libm): the parity tests compare bit-level results that depend on them.  Included once by
 // engine.hip, after its kernels (ma_build_doubles and MA_BUILD_MAX_DOUBLES come from there) and engine_state.h;
-// nlte_tables.h holds the tables of update_grid's host drivers (update_grid_host.h).
+// nlte_tables.h holds the tables of update_grid's host drivers (update_grid_host.h), est_block.h the layout of the
+// estimator block.
 #pragma once
 
 namespace {
@@ -317,39 +318,6 @@ inline CellNumbering number_cells(const artis_geometry *g) {
   std::stable_sort(ne_mgi.begin(), ne_mgi.end(), [&](int a, int b) { return rmin[a] < rmin[b]; });
   for (size_t k = 0; k < ne_mgi.size(); k++) ne_index[ne_mgi[k]] = (int32_t)k;
   return t;
-}
-
-// Estimators: one double block [J | nuJ | ffheat | colheat | rpkt_emiss | gamma | bfheat | scalars(10) |
-// bfrate_raw | radfield J_raw | nuJ_raw | contribcount | compton_emiss] (the nebular sections only when their
-// option is on); offsets in doubles
-struct EstLayout {
-  int64_t nbf_est = 0, nbins_est = 0;  // nebular sections per cell (0 when off)
-  int64_t J, nuJ, ffheat, colheat, rpkt_emiss, gamma, bfheat, scalars, bfrate, rfJ, rfnuJ, rfcount, compton;
-  int64_t n_doubles;
-};
-
-inline EstLayout lay_out_estimators(const artis_atomic_tables *a, const artis_geometry *g, const artis_run_params *rp) {
-  const int np = g->npts_model;
-  const int64_t nion_est = (int64_t)np * a->nelements * a->maxnions;
-  EstLayout L;
-  L.nbf_est = rp->detailed_bf_estimators ? a->nbfcontinua : 0;
-  L.nbins_est = rp->multibin_radfield ? a->radfield_nbins : 0;
-  L.n_doubles = 5 * (int64_t)np + 2 * nion_est + 10 + (int64_t)np * (L.nbf_est + 3 * L.nbins_est) +
-                ((int64_t)np + 1) * ARTIS_EMISS_MAX;
-  L.J = 0;
-  L.nuJ = L.J + np;
-  L.ffheat = L.nuJ + np;
-  L.colheat = L.ffheat + np;
-  L.rpkt_emiss = L.colheat + np;
-  L.gamma = L.rpkt_emiss + np;
-  L.bfheat = L.gamma + nion_est;
-  L.scalars = L.bfheat + nion_est;
-  L.bfrate = L.scalars + 10;
-  L.rfJ = L.bfrate + (int64_t)np * L.nbf_est;
-  L.rfnuJ = L.rfJ + (int64_t)np * L.nbins_est;
-  L.rfcount = L.rfnuJ + (int64_t)np * L.nbins_est;
-  L.compton = L.rfcount + (int64_t)np * L.nbins_est;
-  return L;
 }
 
 // Few-cell models: k_rpkt accumulates the estimators of every non-empty cell per block in LDS, as many of the

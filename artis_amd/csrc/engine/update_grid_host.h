@@ -3,7 +3,8 @@
 // options, nlte_solver.h).  Every caller array is copied in, the solution is computed for the listed cells and
 // every array is copied back on success, so cells not listed round-trip unchanged; on any failure the caller's
 // arrays are not written.  Host code only; included once by engine.hip after engine_state.h, host_tables.h and
-// nlte_tables.h (the kernels and their TeDev / UgDev / NlDev / SfDev / NlMat views come from engine.hip's headers).
+// nlte_tables.h (the kernels and their TeDev / UgDev / NlDev / SfDev / NlMat views come from engine.hip's headers)
+// and before the readout drivers estimators_host.h and spectra_host.h.
 #pragma once
 
 namespace {

@@ -449,6 +449,54 @@ def test_estimator_block_roundtrip_and_rccl(small_model, engine_factory):
     assert np.array_equal(adist.pack_estimators(again), 2 * hb)
 
 
+def test_estimator_block_roundtrip_nebular(engine_factory):
+    """The same identities with both nebular sections in the block (detailed bf-rate and radiation-field bin
+    estimators; the nebular model of test_gpu_nebular.py past the detailed-bf switch-on): the device block is the host
+    pack of the download, bit for bit, with bfrate_raw and the bin counts non-zero in their sections, and the block
+    doubled and written back downloads as twice the estimators."""
+    import ctypes as C
+
+    from artis_amd import dist as adist
+    from artis_amd.model import Model
+    from test_gpu_nebular import NEB
+
+    m = Model(**NEB)
+    eng = engine_factory(m)
+    hip = C.CDLL("libamdhip64.so.7")
+    m.set_timestep(14)
+    eng.upload_cellstate(14)
+    eng.upload(m.init_rpackets(14, 2000, seed=67))
+    eng.zero_estimators()
+    eng.step_resident(14)
+    host = eng.download_estimators()
+    assert host.nbfcontinua > 0 and host.radfield_nbins > 0
+    hb = adist.pack_estimators(host)
+    n = eng.estimator_block_doubles()
+    assert n == len(hb)
+    # the sections as include/artis_gpu.h documents them
+    ncell = host.npts_model
+    off_bf = 5 * ncell + 2 * ncell * host.nelements * host.maxnions + 10
+    off_count = off_bf + ncell * host.nbfcontinua + 2 * ncell * host.radfield_nbins
+    bf, count = slice(off_bf, off_bf + ncell * host.nbfcontinua), slice(off_count, off_count + ncell * host.radfield_nbins)
+    assert host.bfrate_raw.sum() > 0 and host.radfield_count.sum() > 0
+    assert np.array_equal(hb[bf], host.bfrate_raw) and np.array_equal(hb[count], host.radfield_count)
+    dptr = C.c_void_p()
+    assert hip.hipMalloc(C.byref(dptr), C.c_size_t(8 * n)) == 0
+    try:
+        eng.estimator_block_to_device(dptr.value)
+        db = np.zeros(n)
+        assert hip.hipMemcpy(C.c_void_p(db.ctypes.data), dptr, C.c_size_t(8 * n), 2) == 0  # D2H
+        assert np.array_equal(db, hb)
+        assert db[bf].any() and db[count].any()
+        db *= 2.0
+        assert hip.hipMemcpy(dptr, C.c_void_p(db.ctypes.data), C.c_size_t(8 * n), 1) == 0  # H2D
+        eng.estimator_block_from_device(dptr.value)
+    finally:
+        hip.hipFree(dptr)
+    twice = eng.download_estimators()
+    assert np.array_equal(adist.pack_estimators(twice), 2 * hb)
+
+
 @pytest.mark.parametrize("rlc", [1, 2])
 def test_rlc_emiss_rpkt_vs_oracle(small_model, engine_factory, rlc):
     """do_rlc_est 1 / 2 (input.txt line 9 = 2 / 3, input.cc:1976-1979): rlc_emiss_rpkt (grey_emissivities.cc:79-122)

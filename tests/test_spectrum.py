@@ -165,3 +165,43 @@ def test_device_spectra_match_oracle(small_model, abin):
         scale = max(np.abs(a).max(), 1e-300)
         assert np.abs(a - b).max() <= 1e-9 * scale, name
     assert o.flux.sum() > 0 and o.emission.sum() > 0
+
+
+@pytest.mark.gpu
+def test_device_spectra_all_or_nothing(small_model, monkeypatch):
+    """artis_gpu_spectra adds all of its arrays or none: when the device accumulators cannot be allocated
+    (ARTIS_GPU_FAIL_ALLOC_ABOVE below the request) the status is ARTIS_ERR_HIP and no array is touched; the same call
+    without the limit then gives the oracle's spectra."""
+    import ctypes as C
+
+    from artis_amd import Engine
+
+    ERR_HIP = -2  # include/artis_gpu.h
+    nts, nnubins = 9, 300
+    small_model.set_timestep(nts)
+    pk = small_model.init_rpackets(nts, 2000, seed=27)
+    out = ffi.SpectraArrays(small_model.cfg.ntstep, nnubins, small_model.nelements, small_model.maxnions,
+                            emission_res=True, stokes=False)
+    req = ffi.spectra_request(nnubins, 1, -1, (0., 0., 1.))
+    eng = Engine(small_model)
+    try:
+        eng.upload_cellstate(nts)
+        eng.update_packets(nts, pk)
+        for a in out.arrays().values():
+            a[...] = 7.
+        assert 8 * nnubins + sum(a.nbytes for a in out.arrays().values()) > 1 << 20
+        monkeypatch.setenv("ARTIS_GPU_FAIL_ALLOC_ABOVE", str(1 << 20))
+        rc = eng.lib.artis_gpu_spectra(C.byref(req), C.byref(out.struct))
+        monkeypatch.delenv("ARTIS_GPU_FAIL_ALLOC_ABOVE")
+        assert rc == ERR_HIP, (rc, eng.lib.artis_gpu_last_error().decode())
+        assert all(np.all(a == 7.) for a in out.arrays().values())
+        for a in out.arrays().values():
+            a[...] = 0.
+        assert eng.lib.artis_gpu_spectra(C.byref(req), C.byref(out.struct)) == 0
+    finally:
+        eng.close()
+    o = oracle_lib.spectra(small_model, pk, nnubins=nnubins, emission_res=True, stokes=False)
+    for name, a in o.arrays().items():
+        scale = max(np.abs(a).max(), 1e-300)
+        assert np.abs(a - getattr(out, name)).max() <= 1e-9 * scale, name
+    assert o.flux.sum() > 0 and o.emission.sum() > 0
