@@ -72,7 +72,8 @@ DEVFN void nl_fail(const NlDev &N, int mgi, int why) {
 // grid.cc:231-236 / atomic.cc:58-66
 DEVFN double nl_elem_numberdens(const Ctx &K, const NlDev &N, int mgi, int e) {
   const int64_t k = (int64_t)mgi * K.T.nelements + e;
-  return N.abund[k] / N.meanw[k] * (double)N.rho[mgi];
+  const double elem_meanweight = N.meanw[k];  // grid.cc:234: the quotient is taken in double (as te_elem_numberdens)
+  return N.abund[k] / elem_meanweight * (double)N.rho[mgi];
 }
 DEVFN double nl_get_nntot(const Ctx &K, const NlDev &N, int mgi) {
   double nntot = 0.;

@@ -679,17 +679,44 @@ struct NlCall {
     k_sf_combine<<<(nb + 63) / 64, 64, 0, G.stream>>>(KN, N, S, d_pops, nb);
     if (int rc = step("k_sf_combine")) return rc;
     HIPCHK(hipStreamSynchronize(G.stream));  // the batch lists and errbest seeds are reused
+    if (!sf_dumped && n <= SF_DUMP_NMAX && getenv("ARTIS_GPU_NL_DUMP")) {
+      sf_dumped = true;
+      if (int rc = dump_sf(getenv("ARTIS_GPU_NL_DUMP"), sm[0])) return rc;
+    }
     return 0;
   }
 
-  // diagnostics (ARTIS_GPU_NL_DUMP): a pass's rate matrices of the first active cell (tools/nl_dump_cmp.py)
+  // diagnostics (ARTIS_GPU_NL_DUMP): the call's first Spencer-Fano solve, batch slot 0 -- the matrix (column-major),
+  // the right-hand side and the kept solution; only up to SF_DUMP_NMAX points (32 MB)
+  static constexpr int SF_DUMP_NMAX = 2048;
+  bool sf_dumped = false;
+  int dump_sf(const char *prefix, int mgi) const {
+    const size_t n = (size_t)S.n;
+    std::vector<double> hM, hrhs, hbest;
+    if (d2h_vec(hM, (const double *)S.MT, n * n) || d2h_vec(hrhs, S.rhs, n) || d2h_vec(hbest, (const double *)S.best, n))
+      return ARTIS_ERR_HIP;
+    const std::string path = std::string(prefix) + "_sf_gpu.bin";
+    if (FILE *fp = fopen(path.c_str(), "wb")) {
+      const int32_t hdr[2] = {S.n, mgi};
+      fwrite(hdr, sizeof hdr, 1, fp);
+      fwrite(hM.data(), 8, hM.size(), fp);
+      fwrite(hrhs.data(), 8, hrhs.size(), fp);
+      fwrite(hbest.data(), 8, hbest.size(), fp);
+      fclose(fp);
+    }
+    return 0;
+  }
+
+  // diagnostics (ARTIS_GPU_NL_DUMP): a pass's rate matrices of the first active cell (tools/nl_dump_cmp.py), its level
+  // populations, corrected photoionisation coefficients and bf-heating coefficients (by hb_ul)
   int dump_matrices(const char *prefix, int iter) const {
     HIPCHK(hipStreamSynchronize(G.stream));
-    std::vector<double> hA, hbv, hn, hp, hpops, hcorr;
+    std::vector<double> hA, hbv, hn, hp, hpops, hcorr, hhbc;
     std::vector<int32_t> hs;
     if (d2h_vec(hA, M.A, (size_t)L.cell2) || d2h_vec(hbv, M.b, (size_t)L.cell1) ||
         d2h_vec(hn, M.norm, (size_t)L.cell1) || d2h_vec(hp, M.pv, (size_t)L.cell1) ||
-        d2h_vec(hs, M.status, (size_t)ne) || d2h_vec(hpops, d_pops, (size_t)nl) || d2h_vec(hcorr, d_corr, (size_t)ntg))
+        d2h_vec(hs, M.status, (size_t)ne) || d2h_vec(hpops, d_pops, (size_t)nl) ||
+        d2h_vec(hcorr, d_corr, (size_t)ntg) || d2h_vec(hhbc, (const double *)D.hbc, hb.size() * (size_t)nnl))
       return ARTIS_ERR_HIP;
     const std::string path = std::string(prefix) + "_p" + std::to_string(iter) + "_gpu.bin";
     if (FILE *fp = fopen(path.c_str(), "wb")) {
@@ -703,6 +730,10 @@ struct NlCall {
       fwrite(hp.data(), 8, hp.size(), fp);
       fwrite(hpops.data(), 8, hpops.size(), fp);
       fwrite(hcorr.data(), 8, hcorr.size(), fp);
+      const int32_t nhb = (int32_t)hb.size();
+      fwrite(&nhb, 4, 1, fp);
+      fwrite(hb.data(), 4, hb.size(), fp);
+      for (size_t j = 0; j < hb.size(); j++) fwrite(&hhbc[j * nnl + actk[0]], 8, 1, fp);  // hbc[level][iterated cell]
       fclose(fp);
     }
     return 0;

@@ -1549,6 +1549,7 @@ const int32_t *artis_model_ion_ionstage(const artis_model *m) { return m->at.ion
 void artis_model_ion_ground_statweight(const artis_model *m, float *out) {
   for (int ui = 0; ui < m->at.nions_total; ui++) out[ui] = m->at.level_stat_weight[m->at.ion_uniqueleveloffset[ui]];
 }
+const int32_t *artis_model_ion_first_nlte(const artis_model *m) { return m->at.ion_first_nlte; }
 void artis_model_config(const artis_model *m, artis_synth_config *out) { *out = m->cfg; }
 
 void artis_model_run_params(const artis_model *m, artis_run_params *p) {

@@ -44,6 +44,8 @@ def model_lib():
         lib.artis_model_npts_model.restype = C.c_int64
         lib.artis_model_radfield_nbins.argtypes = [C.c_void_p]
         lib.artis_model_total_nlte_levels.argtypes = [C.c_void_p]
+        lib.artis_model_ion_first_nlte.argtypes = [C.c_void_p]
+        lib.artis_model_ion_first_nlte.restype = C.c_void_p
         lib.artis_model_ion_ionstage.argtypes = [C.c_void_p]
         lib.artis_model_ion_ionstage.restype = C.c_void_p
         lib.artis_model_ion_ground_statweight.argtypes = [C.c_void_p, C.c_void_p]
@@ -182,6 +184,13 @@ class Model:
     def ion_ionstage(self):
         p = self._lib.artis_model_ion_ionstage(self._h)
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32)), (self.nions_total,)).copy()
+
+    def nlte_slot_element(self):
+        """element index of every slot of a cell's nlte_pops row (an ion's NLTE levels, then its superlevel)"""
+        p = self._lib.artis_model_ion_first_nlte(self._h)
+        first = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32)), (self.nions_total,)).copy()
+        counts = np.diff(np.append(first, self.total_nlte_levels))
+        return np.repeat(self.ion_element(), counts)
 
     def ion_ground_statweight(self):
         g = np.zeros(self.nions_total, dtype=np.float32)

@@ -56,7 +56,8 @@ inline float &nl_pf(const Ctx &c, const NlteRun &r, int mgi, int e, int i) { ret
 // grid.cc:231-236
 inline double nl_elem_numberdens(const Ctx &c, const NlteRun &r, int mgi, int e) {
   const size_t k = (size_t)mgi * c.at->nelements + e;
-  return r.in->elem_abundance[k] / r.in->elem_meanweight[k] * (double)r.in->rho[mgi];
+  const double elem_meanweight = r.in->elem_meanweight[k];  // grid.cc:234: the quotient is taken in double
+  return r.in->elem_abundance[k] / elem_meanweight * (double)r.in->rho[mgi];
 }
 // atomic.cc:58-66 get_nntot
 double nl_get_nntot(const Ctx &c, const NlteRun &r, int mgi) {
@@ -892,6 +893,22 @@ void nl_solve_spencerfano(const Ctx &c, const NlteRun &r, int mgi, int timestep,
   sf_build(c, r, mgi, M, rhs);
   sf_solve(M.data(), rhs.data(), r.sf.n, y.data());
   sf_analyse(c, r, mgi, y.data(), s, fail);
+  if (const char *dump = getenv("ORACLE_NL_DUMP")) {
+    // diagnostics: the first iterated cell's first solve of this timestep -- the matrix (row-major), the right-hand
+    // side and the solution; only up to 2048 points (32 MB)
+    int first = -1;
+    for (int k = 0; k < r.in->ncells && first < 0; k++)
+      if (!(r.p->initial_iteration || r.in->thick[r.in->mgi[k]] == 1)) first = r.in->mgi[k];
+    if (mgi == first && timestep_last_solved != timestep && r.sf.n <= 2048)
+      if (FILE *fp = fopen((std::string(dump) + "_sf_ora.bin").c_str(), "wb")) {
+        const int32_t hdr[2] = {r.sf.n, mgi};
+        fwrite(hdr, sizeof hdr, 1, fp);
+        fwrite(M.data(), 8, M.size(), fp);
+        fwrite(rhs.data(), 8, rhs.size(), fp);
+        fwrite(y.data(), 8, y.size(), fp);
+        fclose(fp);
+      }
+  }
   if (y_out) *y_out = y;
 }
 
@@ -1105,6 +1122,9 @@ bool nlte_matrix_solve(const double *A, const double *b, int n, double *popvec, 
 }
 
 thread_local std::vector<double> tl_raw_matrix;  // the last rate matrix before normalisation (ORACLE_NL_DUMP)
+// the level populations the last rate matrix was built from and the corrected photoionisation coefficients it read
+// (by level_phixstargets_offset + t; -99: not read by that element)
+thread_local std::vector<double> tl_levelpops, tl_corrphotoion;
 
 // the element's rate matrix, normalised, column-major, with its balance vector and LTE normalisation
 // (nltepop.cc:391-628, 832-920): the five process matrices summed in the reference's order (NT excitation is zero,
@@ -1226,7 +1246,11 @@ int nlte_build(const Ctx &c, const NlteRun &r, int mgi, int e, std::vector<doubl
   }
   A.assign((size_t)D * D, 0.);
   for (size_t q = 0; q < A.size(); q++) A[q] = ((((A[q] + rad_bb[q]) + coll_bb[q]) + rad_bf[q]) + coll_bf[q]) + ntcoll_bf[q];
-  if (getenv("ORACLE_NL_DUMP")) tl_raw_matrix = A;  // diagnostics: the rate matrix before normalisation
+  if (getenv("ORACLE_NL_DUMP")) {  // diagnostics: the rate matrix before normalisation and what it was built from
+    tl_raw_matrix = A;
+    tl_levelpops = tc.pops;
+    tl_corrphotoion.assign(tc.corrphotoioncoeff.begin(), tc.corrphotoioncoeff.begin() + ntg);
+  }
   for (int col = 0; col < D; col++) A[(size_t)col * D + 0] = 1.0;  // normalisation row
   b.assign(D, 0.);
   b[0] = nl_elem_numberdens(c, r, mgi, e);
@@ -1273,6 +1297,10 @@ int nl_solve_nlte_pops_element(const Ctx &c, const NlteRun &r, int e, int mgi, s
       fwrite(norm.data(), 8, norm.size(), fp);
       fwrite(popvec.data(), 8, popvec.size(), fp);
       fwrite(tl_raw_matrix.data(), 8, tl_raw_matrix.size(), fp);
+      const int32_t sizes[2] = {(int32_t)tl_levelpops.size(), (int32_t)tl_corrphotoion.size()};
+      fwrite(sizes, sizeof sizes, 1, fp);
+      fwrite(tl_levelpops.data(), 8, tl_levelpops.size(), fp);
+      fwrite(tl_corrphotoion.data(), 8, tl_corrphotoion.size(), fp);
       fclose(fp);
     }
   }
@@ -1418,6 +1446,28 @@ int oracle_update_grid_nlte(const artis_atomic_tables *at, const artis_run_param
       // update_grid.cc:763-886 solve_Te_nltepops
       std::vector<double> coeff;
       if (nl_calculate_bfheatingcoeffs(c, r, mgi, coeff) != 0) fail = 1;
+      if (const char *dump = getenv("ORACLE_NL_DUMP")) {
+        // diagnostics: the bf-heating coefficient of every level (by unique level index) of the first iterated cell,
+        // then the lowest photoionisation edge frequency
+        int first = -1;
+        for (int q = 0; q < in->ncells && first < 0; q++)
+          if (in->thick[in->mgi[q]] != 1) first = in->mgi[q];
+        if (mgi == first)
+          if (FILE *fp = fopen((std::string(dump) + "_bfheat_ora.bin").c_str(), "wb")) {
+            const int32_t nlev = (int32_t)coeff.size();
+            fwrite(&nlev, 4, 1, fp);
+            fwrite(coeff.data(), 8, coeff.size(), fp);
+            // the lowest photoionisation edge: no bf-heating or photoionisation integral reads the field below it
+            double nu_edge_min = 1e300;
+            for (int e = 0; e < at->nelements; e++)
+              for (int i = 0; i < get_nions(c, e); i++)
+                for (int l = 0; l < get_nlevels(c, e, i); l++)
+                  for (int t = 0; t < get_nphixstargets(c, e, i, l); t++)
+                    nu_edge_min = std::min(nu_edge_min, ARTIS_ONEOVERH * get_phixs_threshold(c, e, i, l, t));
+            fwrite(&nu_edge_min, 8, 1, fp);
+            fclose(fp);
+          }
+      }
       for (int nlte_iter = 0; nlte_iter <= p->nlteiter && !fail; nlte_iter++) {
         iters = nlte_iter + 1;
         if (rp->nt_on && rp->nt_solve_spencerfano) nl_solve_spencerfano(c, r, mgi, p->nts, &fail, nullptr);

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import scipy.linalg
 
+import nebular_ref as nr
 import oracle_lib
 from artis_amd import ffi
 from artis_amd.model import Model
@@ -205,3 +206,111 @@ def test_onezone_solution_is_consistent(onezone_solved):
     assert arr.params.T_min <= arr.Te[c] <= arr.params.T_max and arr.iters[c] >= 2
     Y = arr.nt_ionization_ratecoeff.reshape(-1, ni)[c]
     assert np.all(Y[stage < np.array([stage[el == e].max() for e in el])] > 0)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# The reference's own margins on the cases of tests/test_gpu_nebular_update_grid.py, pinned without a GPU.  Measured
+# by tools/nebular_ref_floors.py; the GPU tests derive the engine's bounds from the same figures (nebular_ref.bound).
+SF_SOLVE_ERROR = 1.4e-15  # tools/nebular_ref_floors.py: Spencer-Fano solution against longdouble, max-norm
+LU_SOLVE_ERROR = 1.9e-06  # tools/nebular_ref_floors.py: rate-matrix solutions against a 40-digit solve, L1
+BIN_W_SPREAD = 2.2e-08    # tools/nebular_ref_floors.py: spread of W P(T_R) / J_bin over the fitted synthetic bins
+
+
+@pytest.mark.parametrize("nbins,T_R_min", nr.SYNTH_BIN_CASES)
+def test_bin_fits_synthetic_oracle(nbins, T_R_min):
+    """fit_parameters on bins with known answers (nebular_ref.SyntheticBins: Planck spectra from 30-digit integrals
+    below, inside and above [T_R_min, T_R_max], an empty bin, the W > 1e4 fallback to T_R_max, the -99 outcome, T_e in
+    the last bin): every kind ends in its class; around every Brent root the 30-digit mean-frequency residual changes
+    sign within 1.5e-4 (the 1e-4 bracket of find_T_R); W P(T_R) / J_bin is the same for every bin to a float32 ulp."""
+    sb = nr.SyntheticBins(nr.oracle_estimators, nbins, T_R_min)
+    a = sb.arr.copy()
+    assert oracle_lib.update_grid_nlte(sb.model, sb.nt, a, params=sb.params, nthreads=8) == 0
+    want = {"planck": None, **sb.expected()}
+    classes = {}
+    for (c, b), (kind, T, J) in sb.bins.items():
+        cls = sb.outcome(a, c, b)
+        if kind == "planck":
+            want_cls = "min" if T < T_R_min else "max" if T > nr.T_R_MAX else "root"
+            assert cls == want_cls, (c, b, T, cls)
+            if cls == "root":  # the spectrum's own temperature, to the bracket
+                assert a.bin_TR[c * nbins + b] == pytest.approx(T, rel=nr.ROOT_RTOL)
+        else:
+            assert cls == want[kind], (c, b, kind, cls)
+        classes[cls] = classes.get(cls, 0) + 1
+    assert set(classes) == {"empty", "minus99", "min", "max", "Te", "root"} and classes["root"] == 4, classes
+    nroot, spread = sb.check(a, "oracle")
+    assert nroot == 4
+    assert spread <= 10 * BIN_W_SPREAD and spread <= 2 * nr.F32_ULP, spread
+
+
+@pytest.mark.parametrize("sfpts,sf_emax", nr.SF_SHAPES)
+def test_sf_solution_against_longdouble(sfpts, sf_emax, tmp_path, monkeypatch):
+    """sfmatrix_solve on the one-zone model's own matrix at the grid sizes of the GPU tests: the kept solution against
+    a plain longdouble back substitution, a finite solution with heating fractions just below one and Auger
+    probabilities that add up to one."""
+    prefix = str(tmp_path / "sf")
+    monkeypatch.setenv("ORACLE_NL_DUMP", prefix)
+    m, p, nt, arr, nts = nr.onezone_case(nr.oracle_estimators, 12, True, sfpts=sfpts, sf_emax=sf_emax, one_pass=True,
+                                         npkts=6000)
+    assert oracle_lib.update_grid_nlte(m, nt, arr, params=p, nthreads=8) == 0
+    c = int(arr.mgi_list[0])
+    mgi, M, rhs, y = nr.read_dump_sf(prefix + "_sf_ora.bin", column_major=False)
+    assert mgi == c and M.shape == (sfpts, sfpts) and np.all(np.isfinite(y)) and np.all(np.diag(M) > 0)
+    assert nr.sf_solution_error(M, rhs, y) <= 10 * SF_SOLVE_ERROR
+    assert 0.9999 < arr.nt_frac_heating[c] < 1.
+    psum = arr.nt_prob_num_auger.reshape(m.npts_model, m.nions_total, -1)[c].sum(axis=1)
+    assert np.all((np.abs(psum - 1.) < 1e-6) | (psum == 0.)), psum
+
+
+def test_lu_solution_against_high_precision(tmp_path, monkeypatch):
+    """nltepop_matrix_solve on the one-zone model's first-pass rate matrices against a 40-digit solve of the same
+    systems: the L1 error stays within 10 x the committed floor (populations spanning 40 decades; LAPACK on random
+    well-conditioned systems, above, reaches 1e-10)."""
+    prefix = str(tmp_path / "nl")
+    monkeypatch.setenv("ORACLE_NL_DUMP", prefix)
+    m, p, nt, arr, nts = nr.onezone_case(nr.oracle_estimators, 12, True, sfpts=48, sf_emax=500., one_pass=True,
+                                         npkts=6000)
+    assert oracle_lib.update_grid_nlte(m, nt, arr, params=p, nthreads=8) == 0
+    checked = 0
+    for e in range(m.nelements):
+        fn = f"{prefix}_p0_ora_e{e}.bin"
+        if not os.path.exists(fn):
+            continue
+        d = nr.read_dump_oracle(fn)
+        D = d["D"]
+        err, ref = nr.lu_solution_error(d["A"].reshape(D, D).T, d["b"], d["norm"], d["pv"])
+        assert d["status"] == 0 and err <= 10 * LU_SOLVE_ERROR, (e, err)
+        assert ref.sum() == pytest.approx(d["b"][0], rel=1e-12)  # row 0: the populations add up to the element's
+        assert len(d["pops"]) == m.nlevels_total and np.all(d["pops"] >= 0.)
+        checked += 1
+    assert checked >= 2
+
+
+def test_element_number_density_quotient_in_double():
+    """get_elem_numberdens (grid.cc:231-236) promotes the element's mean weight to double before dividing the float
+    abundance by it.  The adiabatic cooling rate p dV / V with p = n_tot k T_e, n_tot = sum_Z Z n_element
+    (thermalbalance.cc:380-388) shows it: a float quotient moves it by up to 6e-8, the double one reproduces it to
+    rounding."""
+    m, p, nt, arr, nts = nr.onezone_case(nr.oracle_estimators, 12, True, sfpts=48, sf_emax=500., one_pass=True,
+                                         npkts=6000)
+    a = arr.copy()
+    assert oracle_lib.update_grid_nlte(m, nt, a, params=p, nthreads=8) == 0
+    c = int(arr.mgi_list[0])
+    ne = m.nelements
+    hdr = ffi.AtomicHeader.from_address(m.atomic)
+    Z = np.ctypeslib.as_array(C.cast(hdr.elem_anumber, C.POINTER(C.c_int32)), (ne,)).astype(np.float64)
+    ab, mw = arr.elem_abundance.reshape(-1, ne)[c], arr.elem_meanweight.reshape(-1, ne)[c]
+    assert ab.dtype == mw.dtype == np.float32
+    KB = 1.38064852e-16
+    par = arr.params
+    vol = arr.vol_init[c]
+    dV_over_V = (3 * vol / par.tmin ** 3 * par.t_current_te ** 2) / (vol * (par.t_current_te / par.tmin) ** 3)
+
+    def adiabatic(quotient, T_e):
+        return float(np.sum(quotient * np.float64(arr.rho[c]) * Z)) * KB * T_e * dV_over_V
+
+    got = a.rates.reshape(-1, 8)[c, 3]
+    in_double = [adiabatic(ab / mw.astype(np.float64), T) for T in (par.T_min, par.T_max)]
+    in_float = [adiabatic((ab / mw).astype(np.float64), T) for T in (par.T_min, par.T_max)]
+    assert min(abs(got / v - 1.) for v in in_double) < 1e-14
+    assert min(abs(got / v - 1.) for v in in_float) > 1e-10  # the case can tell the two apart
