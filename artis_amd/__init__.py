@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "artis_gpu_comm_unique_id", "artis_gpu_comm_init", "artis_gpu_estimators_allreduce", "artis_gpu_comm_finalize",
     "artis_gpu_solve_temperatures", "artis_gpu_last_te_ms", "artis_gpu_prepare_temperatures",
     "artis_gpu_update_grid_nlte", "artis_gpu_last_nlte_ms", "artis_gpu_table_info", "artis_gpu_vpkt_last_drains",
+    "artis_gpu_ratecoeff_tables", "artis_gpu_last_ratecoeff_ms",
 ]
 
 _gpu_lib = None
@@ -103,6 +104,9 @@ def gpu_lib():
         L.artis_gpu_update_grid_nlte.argtypes = [C.POINTER(ffi.NtShells), C.POINTER(ffi.NlteParams),
                                                  C.POINTER(ffi.NlteCells)]
         L.artis_gpu_last_nlte_ms.restype = C.c_double
+        L.artis_gpu_ratecoeff_tables.argtypes = [C.c_int, vp, C.POINTER(ffi.RatecoeffRequest),
+                                                 C.POINTER(ffi.RatecoeffOut)]
+        L.artis_gpu_last_ratecoeff_ms.restype = C.c_double
         _gpu_lib = L
     return _gpu_lib
 

@@ -37,6 +37,7 @@
 #include "qag.h"
 #include "te_solver.h"
 #include "nlte_solver.h"
+#include "ratecoeff_lut.h"
 
 // ================================================================================================= kernels
 
@@ -1577,6 +1578,8 @@ int run_wavefront(int64_t n, int nts, double t2) {
 // the readout side: the estimator block and its all-reduce; the spectra and the line trace
 #include "estimators_host.h"
 #include "spectra_host.h"
+// ratecoefficients_init's lookup tables: artis_gpu_ratecoeff_tables (needs no engine)
+#include "ratecoeff_host.h"
 
 extern "C" {
 int artis_gpu_abi_version(void) { return ARTIS_GPU_ABI_VERSION; }

@@ -98,31 +98,36 @@ DEVFN void qag_qk61(const F &f, double a, double b, double *s_f, double *result,
 }
 
 // The error list and its order (the arrays qpsrt walks, O(size) dependent reads per bisection) live in LDS for the
-// first QAG_LDS intervals; intervals beyond that, up to GSLWSIZE, in the wave's global workspace.
+// first CAP intervals; intervals beyond that, up to GSLWSIZE, in the wave's global workspace.  CAP is a parameter of
+// the list type: the per-cell integrals (k_corrphot_integral, k_nl_bfheat) keep QAG_LDS entries, the lookup-table
+// integrals of ratecoeff_lut.h, which end after a few bisections, a few dozen.  Where an entry lives changes no value.
 #define QAG_LDS 4096
-struct QagLists {
+template <int CAP>
+struct QagListsT {
   double *s_el;
   int32_t *s_ord;
   double *g_el;
   int32_t *g_ord;
-  DEVFN double el(int i) const { return i < QAG_LDS ? s_el[i] : g_el[i]; }
+  DEVFN double el(int i) const { return i < CAP ? s_el[i] : g_el[i]; }
   DEVFN void set_el(int i, double v) const {
-    if (i < QAG_LDS)
+    if (i < CAP)
       s_el[i] = v;
     else
       g_el[i] = v;
   }
-  DEVFN int32_t ord(int i) const { return i < QAG_LDS ? s_ord[i] : g_ord[i]; }
+  DEVFN int32_t ord(int i) const { return i < CAP ? s_ord[i] : g_ord[i]; }
   DEVFN void set_ord(int i, int32_t v) const {
-    if (i < QAG_LDS)
+    if (i < CAP)
       s_ord[i] = v;
     else
       g_ord[i] = v;
   }
 };
+using QagLists = QagListsT<QAG_LDS>;
 
 // integration/qpsrt.c on the wave's workspace (ordered list of error indices)
-DEVFN void qag_qpsrt(const QagLists &Q, int size, int &nrmax, int &imax) {
+template <typename L>
+DEVFN void qag_qpsrt(const L &Q, int size, int &nrmax, int &imax) {
   const int last = size - 1;
   const int limit = QAG_LIMIT;
   int i_nrmax = nrmax;
@@ -156,12 +161,14 @@ DEVFN void qag_qpsrt(const QagLists &Q, int size, int &nrmax, int &imax) {
   nrmax = i_nrmax;
 }
 
-// integration/qag.c; returns the GSL status (0, 18 GSL_EROUND, 21 GSL_ESING, 11 GSL_EMAXITER, 5 GSL_EFAILED)
-template <typename F>
+// integration/qag.c; returns the GSL status (0, 18 GSL_EROUND, 21 GSL_ESING, 11 GSL_EMAXITER, 5 GSL_EFAILED);
+// *intervals (optional): the workspace size at return
+template <typename F, typename L>
 DEVFN int qag61(const F &f, double a, double b, double epsabs, double epsrel, double *al, double *bl, double *rl,
-                const QagLists &Q, int32_t *lev, double *s_f, double *result, double *abserr) {
+                const L &Q, int32_t *lev, double *s_f, double *result, double *abserr, int *intervals = nullptr) {
   const int limit = QAG_LIMIT;
   int size = 0, nrmax = 0, imax = 0;
+  if (intervals) *intervals = 1;
   al[0] = a;
   bl[0] = b;
   rl[0] = 0.0;
@@ -247,6 +254,7 @@ DEVFN int qag61(const F &f, double a, double b, double epsabs, double epsrel, do
   for (int k = 0; k < size; k++) result_sum += rl[k];
   *result = result_sum;
   *abserr = errsum;
+  if (intervals) *intervals = size;
   if (errsum <= tolerance) return 0;
   if (error_type == 2) return 18;
   if (error_type == 3) return 21;

@@ -889,3 +889,115 @@ void artis_free_nt_data(artis_nt_data *d) {
   d->storage = nullptr;
   std::memset(&d->shells, 0, sizeof d->shells);
 }
+
+// ------------------------------------------------------------------------------------------------ ratecoeff.dat
+namespace {
+// the loop of write_ratecoeff_dat / read_ratecoeff_dat over (element, non-top ion, ionising level, target, iter)
+// with the get_bflutindex position of each row; false from `row` stops it
+template <typename Row>
+bool ratecoeff_rows(const artis_atomic_tables *a, const Row &row) {
+  for (int e = 0; e < a->nelements; e++)
+    for (int i = 0; i < a->elem_nions[e] - 1; i++) {
+      const int ui = a->elem_uniqueionoffset[e] + i;
+      for (int l = 0; l < a->ion_ionisinglevels[ui]; l++) {
+        const int ul = a->ion_uniqueleveloffset[ui] + l;
+        for (int t = 0; t < a->level_nphixstargets[ul]; t++) {
+          const int64_t col = -1 - (int64_t)a->level_cont_index[ul] + t;
+          if (col < 0 || col >= a->nbfcontinua) return false;
+          for (int iter = 0; iter < a->tablesize; iter++)
+            if (!row((size_t)iter * a->nbfcontinua + (size_t)col)) return false;
+        }
+      }
+    }
+  return true;
+}
+bool ratecoeff_args_ok(const artis_atomic_tables *a, const char *const md5[3]) {
+  if (!a || !md5 || !md5[0] || !md5[1] || !md5[2] || a->tablesize <= 0 || a->nbfcontinua <= 0 || !a->elem_anumber ||
+      !a->elem_nions || !a->elem_uniqueionoffset || !a->ion_ionstage || !a->ion_nlevels || !a->ion_ionisinglevels ||
+      !a->ion_uniqueleveloffset || !a->level_nphixstargets || !a->level_cont_index)
+    return false;
+  for (int k = 0; k < 3; k++)
+    if (std::strlen(md5[k]) != 32 || std::strpbrk(md5[k], " \t\r\n")) return false;
+  return true;
+}
+}  // namespace
+
+// ratecoeff.cc:195-244
+int artis_write_ratecoeff_dat(const char *filename, const artis_atomic_tables *a, const artis_ratecoeff_out *tables,
+                              const char *const md5[3]) {
+  if (!ratecoeff_args_ok(a, md5) || !tables || !tables->spontrecombcoeff || !tables->bfcooling_coeff)
+    return ARTIS_ERR_BAD_ARGUMENT;
+  File out(filename, "w");
+  if (!out.f) return ARTIS_ERR_BAD_ARGUMENT;
+  FILE *f = out.f;
+  for (int k = 0; k < 3; k++) std::fprintf(f, "%32s\n", md5[k]);
+  std::fprintf(f, "%g %g %d %d\n", a->mintemp, a->maxtemp, a->tablesize, a->nlines);
+  for (int e = 0; e < a->nelements; e++)
+    for (int i = 0; i < a->elem_nions[e]; i++) {
+      const int ui = a->elem_uniqueionoffset[e] + i;
+      std::fprintf(f, "%d %d %d %d\n", a->elem_anumber[e], a->ion_ionstage[ui], a->ion_nlevels[ui],
+                   a->ion_ionisinglevels[ui]);
+    }
+  const bool ok = ratecoeff_rows(a, [&](size_t idx) {
+    std::fprintf(f, "%g %g", tables->spontrecombcoeff[idx], tables->bfcooling_coeff[idx]);
+    const double corrphotoioncoeff = tables->corrphotoioncoeff ? tables->corrphotoioncoeff[idx] : -1.0;
+    const double bfheating_coeff = tables->bfheating_coeff ? tables->bfheating_coeff[idx] : -1.0;
+    std::fprintf(f, " %g %g\n", corrphotoioncoeff, bfheating_coeff);
+    return true;
+  });
+  return (!ok || std::ferror(f)) ? ARTIS_ERR_BAD_ARGUMENT : 0;
+}
+
+// ratecoeff.cc:49-193
+int artis_read_ratecoeff_dat(const char *filename, const artis_atomic_tables *a, const char *const md5[3],
+                             artis_ratecoeff_out *tables, int32_t *have_corrphotoioncoeff,
+                             int32_t *have_bfheating_coeff) {
+  if (!ratecoeff_args_ok(a, md5) || !tables || !tables->spontrecombcoeff || !tables->bfcooling_coeff)
+    return ARTIS_ERR_BAD_ARGUMENT;
+  File in(filename, "r");
+  if (!in.f) return 0;  // "No ratecoeff.dat file available"
+  FILE *f = in.f;
+  for (int k = 0; k < 3; k++) {
+    char hash_in[33];
+    if (std::fscanf(f, "%32s\n", hash_in) != 1) return ARTIS_ERR_BAD_ARGUMENT;
+    if (std::strcmp(md5[k], hash_in) != 0) return 0;
+  }
+  float T_min = 0.f, T_max = 0.f;
+  int in_tablesize = 0, in_nlines = 0;
+  if (std::fscanf(f, "%g %g %d %d\n", &T_min, &T_max, &in_tablesize, &in_nlines) != 4) return ARTIS_ERR_BAD_ARGUMENT;
+  if (!(T_min == a->mintemp && T_max == a->maxtemp && in_tablesize == a->tablesize && in_nlines == a->nlines))
+    return 0;
+  for (int e = 0; e < a->nelements; e++)
+    for (int i = 0; i < a->elem_nions[e]; i++) {
+      const int ui = a->elem_uniqueionoffset[e] + i;
+      int in_element, in_ionstage, in_levels, in_ionisinglevels;
+      if (std::fscanf(f, "%d %d %d %d\n", &in_element, &in_ionstage, &in_levels, &in_ionisinglevels) != 4)
+        return ARTIS_ERR_BAD_ARGUMENT;
+      if (a->elem_anumber[e] != in_element || a->ion_ionstage[ui] != in_ionstage || a->ion_nlevels[ui] != in_levels ||
+          a->ion_ionisinglevels[ui] != in_ionisinglevels)
+        return 0;
+    }
+  bool have_gamma = true, have_heat = true, parsed = true;
+  const bool ok = ratecoeff_rows(a, [&](size_t idx) {
+    double alpha_sp, bfcooling_coeff, corrphotoioncoeff, bfheating_coeff;
+    if (std::fscanf(f, "%lg %lg %lg %lg\n", &alpha_sp, &bfcooling_coeff, &corrphotoioncoeff, &bfheating_coeff) != 4)
+      return parsed = false;
+    tables->spontrecombcoeff[idx] = alpha_sp;
+    tables->bfcooling_coeff[idx] = bfcooling_coeff;
+    if (corrphotoioncoeff >= 0) {
+      if (tables->corrphotoioncoeff) tables->corrphotoioncoeff[idx] = corrphotoioncoeff;
+    } else {
+      have_gamma = false;
+    }
+    if (bfheating_coeff >= 0) {
+      if (tables->bfheating_coeff) tables->bfheating_coeff[idx] = bfheating_coeff;
+    } else {
+      have_heat = false;
+    }
+    return true;
+  });
+  if (!ok || !parsed) return ARTIS_ERR_BAD_ARGUMENT;
+  if (have_corrphotoioncoeff) *have_corrphotoioncoeff = have_gamma;
+  if (have_bfheating_coeff) *have_bfheating_coeff = have_heat;
+  return 1;
+}

@@ -22,9 +22,14 @@
 // ARTIS_DRIVER_EXSPEC_TRACE="tmin_d,tmax_d,lmin_A,lmax_A[;...]" (only with ARTIS_DRIVER_EXSPEC): also the per-line
 // emission / absorption trace of those regions (days and Angstroms, as the reference's traceemissabs_ defines;
 // PacketEngine::line_trace) into <dir>/emission_absorption_trace.out.
+// ARTIS_DRIVER_RATECOEFF=1: ratecoefficients_init on the GPU before the engine exists (PacketEngine::ratecoeff_tables
+// at RATECOEFF_INTEGRAL_ACCURACY = ARTIS_DRIVER_RATECOEFF_EPSREL, default 1e-3): the engine and the artis_te_tables of
+// ARTIS_DRIVER_TE are then made from these tables instead of the model generator's.  Prints
+// "ratecoeff_tables ms <wall> kernel_ms <device> integrals <n> status0 <n with GSL status 0>".
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -303,7 +308,41 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "model synthesis failed\n");
     return 1;
   }
-  const artis_atomic_tables &at = *artis_model_atomic(m);
+  // the atomic tables the engine is made from: the model's, with the lookup tables replaced when they are built here
+  artis_atomic_tables at_run = *artis_model_atomic(m);
+  artis_te_tables te_run = *artis_model_te_tables(m);
+  std::vector<double> rc_alpha, rc_gamma, rc_heat, rc_cool;
+  std::vector<float> rc_ion_alpha;
+  const char *rce = std::getenv("ARTIS_DRIVER_RATECOEFF");
+  if (rce && rce[0] == '1') {
+    const size_t lutsize = (size_t)at_run.tablesize * at_run.nbfcontinua;
+    for (auto *v : {&rc_alpha, &rc_gamma, &rc_heat, &rc_cool}) v->assign(lutsize, 0.);
+    rc_ion_alpha.assign((size_t)at_run.nions_total * at_run.tablesize, 0.f);
+    std::vector<uint8_t> status(4 * lutsize, 255);
+    const char *eps = std::getenv("ARTIS_DRIVER_RATECOEFF_EPSREL");
+    artis_ratecoeff_request req{};
+    req.epsrel = (eps && std::atof(eps) > 0) ? std::atof(eps) : 1e-3;
+    artis_ratecoeff_out out{};
+    out.spontrecombcoeff = rc_alpha.data();
+    out.corrphotoioncoeff = rc_gamma.data();
+    out.bfheating_coeff = rc_heat.data();
+    out.bfcooling_coeff = rc_cool.data();
+    out.ion_alpha_sp = rc_ion_alpha.data();
+    out.status = status.data();
+    const auto t0 = std::chrono::steady_clock::now();
+    artis_amd::PacketEngine::ratecoeff_tables(0, at_run, req, out);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    long long status0 = 0;
+    for (uint8_t st : status) status0 += st == 0;
+    std::printf("ratecoeff_tables ms %.3f kernel_ms %.3f integrals %lld status0 %lld\n", ms,
+                artis_gpu_last_ratecoeff_ms(), (long long)status.size(), status0);
+    at_run.spontrecombcoeff = rc_alpha.data();
+    at_run.corrphotoioncoeff = rc_gamma.data();
+    at_run.bfcooling_coeff = rc_cool.data();
+    te_run.bfheating_coeff = rc_heat.data();
+    te_run.ion_alpha_sp = rc_ion_alpha.data();
+  }
+  const artis_atomic_tables &at = at_run;
   artis_run_params rp;
   artis_model_run_params(m, &rp);
   const int64_t np = artis_model_npts_model(m);
@@ -415,7 +454,7 @@ int main(int argc, char **argv) {
       put(o, c.meanw);
       const double pv[4] = {c.par.t_current, c.par.tmin, c.prep.deltat, c.prep.tratmid};
       o.write((const char *)pv, sizeof pv);
-      const artis_te_tables &tab = *artis_model_te_tables(m);
+      const artis_te_tables &tab = te_run;
       engine.prepare_temperatures(tab, c.par, c.prep, c.cells);
       for (const auto *v : {&c.TR_new, &c.W_new, &c.TJ_new}) put(o, *v);
       // the solution reads the prepared radiation field (the estimator inputs already point at the prepared arrays)

@@ -55,6 +55,11 @@ void PacketEngine::unique_id(unsigned char id[ARTIS_COMM_ID_BYTES]) {
   check(artis_gpu_comm_unique_id(id), "artis_gpu_comm_unique_id");
 }
 
+void PacketEngine::ratecoeff_tables(int device, const artis_atomic_tables &atomic,
+                                    const artis_ratecoeff_request &request, artis_ratecoeff_out &out) {
+  check(artis_gpu_ratecoeff_tables(device, &atomic, &request, &out), "artis_gpu_ratecoeff_tables");
+}
+
 void PacketEngine::comm_init(int rank, int nranks, const unsigned char id[ARTIS_COMM_ID_BYTES]) {
   check(artis_gpu_comm_init(rank, nranks, id), "artis_gpu_comm_init");
 }

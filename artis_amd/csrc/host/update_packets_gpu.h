@@ -36,6 +36,13 @@ class PacketEngine {
   // Multi-GPU (one process per GPU): join the RCCL communicator of all ranks.  Rank 0 makes the id with
   // unique_id(); the host distributes it (MPI_Bcast in sn3d).
   static void unique_id(unsigned char id[ARTIS_COMM_ID_BYTES]);
+
+  // ratecoefficients_init's lookup tables on device `device` (artis_gpu_ratecoeff_tables: the integrals of
+  // precalculate_rate_coefficient_integrals and precalculate_ion_alpha_sp, ratecoeff.cc:450-625, 970-992).  Needs no
+  // engine -- the tables it fills are the LUT members of the artis_atomic_tables a PacketEngine is then made from,
+  // and its artis_te_tables -- and leaves a live one untouched.
+  static void ratecoeff_tables(int device, const artis_atomic_tables &atomic, const artis_ratecoeff_request &request,
+                               artis_ratecoeff_out &out);
   void comm_init(int rank, int nranks, const unsigned char id[ARTIS_COMM_ID_BYTES]);
 
   // update_packets followed by the reference's mpi_reduce_estimators (sn3d.cc:316-377, radfield.cc:1502-1564)

@@ -640,6 +640,39 @@ class AtomicHeader(C.Structure):
                 ("elem_uniqueionoffset", C.c_void_p)]
 
 
+class AtomicTables(C.Structure):
+    """artis_atomic_tables in full (include/artis_gpu.h); tests/test_ratecoeff.py checks its size and the offsets of
+    the three LUT members against the compiler's.  AtomicHeader is its leading part."""
+    _fields_ = AtomicHeader._fields_ + [(n, C.c_void_p) for n in (
+        "ion_ionstage", "ion_nlevels", "ion_uniqueleveloffset", "ion_ionisinglevels", "ion_maxrecombininglevel",
+        "ion_coolingoffset", "ion_ncoolingterms", "ion_ionpot",
+        "level_epsilon", "level_stat_weight", "level_nuptrans", "level_uptrans_offset", "level_ndowntrans",
+        "level_downtrans_offset", "level_nphixstargets", "level_phixstargets_offset", "level_cont_index",
+        "level_closestgroundlevelcont", "level_phixstable", "uptrans_lineindex", "downtrans_lineindex",
+        "phixstarget_levelindex", "phixstarget_probability", "phixs_xs",
+        "line_nu", "line_einstein_A", "line_osc_strength", "line_coll_str", "line_elementindex", "line_ionindex",
+        "line_upperlevelindex", "line_lowerlevelindex", "line_forbidden",
+        "allcont_nu_edge", "allcont_element", "allcont_ion", "allcont_level", "allcont_phixstargetindex",
+        "allcont_upperlevel", "allcont_phixstable", "allcont_probability", "allcont_index_in_groundphixslist",
+        "groundcont_nu_edge", "groundcont_element", "groundcont_ion", "groundcont_level",
+        "groundcont_phixstargetindex",
+        "spontrecombcoeff", "corrphotoioncoeff", "bfcooling_coeff",
+        "coolinglist_type", "coolinglist_element", "coolinglist_ion", "coolinglist_level", "coolinglist_upperlevel",
+        "ion_nlevels_nlte", "ion_first_nlte")] + [
+        ("total_nlte_levels", C.c_int32), ("radfield_nbins", C.c_int32), ("radfield_nu_upper", C.c_void_p),
+        ("radfield_nu_lower_first", C.c_double)]
+
+
+# the rate-coefficient lookup tables on the device (include/artis_gpu.h artis_ratecoeff_*)
+class RatecoeffRequest(C.Structure):
+    _fields_ = [("epsrel", C.c_double), ("list_lds_capacity", C.c_int32), ("pad0", C.c_int32)]
+
+
+class RatecoeffOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("spontrecombcoeff", "corrphotoioncoeff", "bfheating_coeff",
+                                           "bfcooling_coeff", "ion_alpha_sp", "status", "intervals")]
+
+
 MH = 1.67352e-24
 
 

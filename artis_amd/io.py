@@ -36,6 +36,9 @@ def lib():
         L.artis_free_model.argtypes = [C.POINTER(EjectaModel)]
         L.artis_free_model.restype = None
         L.artis_read_abundances.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, vp, vp]
+        L.artis_write_ratecoeff_dat.argtypes = [C.c_char_p, vp, C.POINTER(ffi.RatecoeffOut), C.c_char_p * 3]
+        L.artis_read_ratecoeff_dat.argtypes = [C.c_char_p, vp, C.c_char_p * 3, C.POINTER(ffi.RatecoeffOut),
+                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         _LIB = L
     return _LIB
 

@@ -823,6 +823,42 @@ typedef struct artis_nlte_cells {
 int artis_gpu_update_grid_nlte(const artis_nt_shells *nt, const artis_nlte_params *params, artis_nlte_cells *cells);
 double artis_gpu_last_nlte_ms(void);  /* device time (ms) of the last artis_gpu_update_grid_nlte */
 
+/* ------------------------------------------------------------------------------------------------------------ */
+/* The rate-coefficient lookup tables of ratecoefficients_init (ratecoeff.cc:994-1023) on the device: for every    */
+/* (ionising level, phixs target, table temperature) the four gsl_integration_qag(GAUSS61) integrals of            */
+/* precalculate_rate_coefficient_integrals (ratecoeff.cc:450-625; alpha_sp, gammacorr, approx_bfheating, bfcooling */
+/* integrands, ratecoeff.cc:249-394) over [nu_threshold, nu_threshold * last_phixs_nuovernuedge] with epsabs 0 and */
+/* epsrel = RATECOEFF_INTEGRAL_ACCURACY (1e-2 classic, 1e-3 the other option files), scaled and clamped as         */
+/* ratecoeff.cc:524-619 (a negative or non-finite value becomes 0), then precalculate_ion_alpha_sp                */
+/* (ratecoeff.cc:970-992) on the host.  read_recombrate_file / scale_level_phixs (the calibration file) is not     */
+/* applied.                                                                                                        */
+/* Callable before artis_gpu_init: of `atomic` it reads the counts, the LUT grid (tablesize, mintemp, maxtemp), the */
+/* cross-section grid, the element / ion / level arrays and the photoionisation targets and tables; the three LUT  */
+/* pointers may be NULL.  It leaves a live engine untouched: stream, events and device memory are its own and are   */
+/* released before it returns.  Nothing is accumulated, so two calls return the same bits.                        */
+/* ARTIS_ERR_BAD_ARGUMENT (artis_gpu_last_error starts with "ratecoeff_tables:"; no HIP call is made, the arrays    */
+/* are untouched): a NULL argument or needed array; epsrel not > 0; tablesize < 2; not 0 < mintemp < maxtemp; an    */
+/* unknown list_lds_capacity; atomic tables whose indices do not fit their counts.                                */
+/* ------------------------------------------------------------------------------------------------------------ */
+typedef struct artis_ratecoeff_request {
+  double epsrel;               /* RATECOEFF_INTEGRAL_ACCURACY */
+  int32_t list_lds_capacity;   /* entries of qag's error list kept in LDS: 0 = default (64), 64 or 16; the rest
+                                  of GSLWSIZE lives in device memory.  Changes no result. */
+  int32_t pad0;
+} artis_ratecoeff_request;
+typedef struct artis_ratecoeff_out {
+  /* [tablesize * nbfcontinua], get_bflutindex order; OVERWRITTEN.  corrphotoioncoeff / bfheating_coeff NULL: that
+     integral is skipped (NO_LUT_PHOTOION / NO_LUT_BFHEATING builds) */
+  double *spontrecombcoeff, *corrphotoioncoeff, *bfheating_coeff, *bfcooling_coeff;
+  float *ion_alpha_sp;   /* [nions_total * tablesize] elements[].ions[].Alpha_sp; OVERWRITTEN */
+  uint8_t *status;       /* optional [4][tablesize * nbfcontinua]: GSL status per integral, in the order
+                            alpha_sp, gammacorr, bfheating, bfcooling (0 for a skipped one) */
+  int32_t *intervals;    /* optional, same shape: workspace size at return (0 for a skipped integral) */
+} artis_ratecoeff_out;
+int artis_gpu_ratecoeff_tables(int device, const artis_atomic_tables *atomic, const artis_ratecoeff_request *req,
+                               artis_ratecoeff_out *out);
+double artis_gpu_last_ratecoeff_ms(void);  /* device time (ms) of the last call's kernel (k_ratecoeff_lut) */
+
 #define ARTIS_GPU_ABI_VERSION 11 /* 2: gamma / pellet / non-thermal path (artis_gamma_spectra and appended fields);
                                     3: virtual packets (artis_vpkt_params / artis_vpkt_result);
                                     4: artis_run_params.excitation_temperature;
@@ -839,7 +875,8 @@ double artis_gpu_last_nlte_ms(void);  /* device time (ms) of the last artis_gpu_
                                    11: artis_gpu_init refuses unsupported option values; rlc_emiss_rpkt into
                                        rpkt_emiss for do_rlc_est 1 / 2; artis_gpu_table_info's level-mode entries;
                                        (still 11, an appended entry point breaks no caller) artis_gpu_spectra_res
-                                       and artis_spectra_res_request; artis_gpu_line_trace and its structs */
+                                       and artis_spectra_res_request; artis_gpu_line_trace and its structs;
+                                       artis_gpu_ratecoeff_tables and its structs */
 int artis_gpu_abi_version(void);
 
 #ifdef __cplusplus

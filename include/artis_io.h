@@ -149,6 +149,27 @@ int artis_read_nt_data(const char *dir, int nelements, const int32_t *anumber, c
                        const int32_t *nions, int sfpts, double sf_emin, double sf_emax, artis_nt_data *out);
 void artis_free_nt_data(artis_nt_data *d);
 
+/* ratecoeff.dat (write_ratecoeff_dat / read_ratecoeff_dat, ratecoeff.cc:49-244), the file through which
+ * ratecoefficients_init hands its lookup tables to later runs: the three 32-character MD5 hashes of adata.txt,
+ * compositiondata.txt and the phixs file (given by the caller, who has the files), the line "MINTEMP MAXTEMP
+ * TABLESIZE nlines", one line "Z ionstage nlevels ionisinglevels" per ion, then for every (element, non-top ion,
+ * ionising level, phixs target, table temperature) a row "%g %g %g %g": alpha_sp, bfcooling_coeff,
+ * corrphotoioncoeff, bfheating_coeff.  `tables` are [tablesize * nbfcontinua] in get_bflutindex order (the arrays of
+ * artis_gpu_ratecoeff_tables; ion_alpha_sp, status and intervals are not part of the file).
+ * write: a NULL corrphotoioncoeff / bfheating_coeff is written as -1 (NO_LUT_PHOTOION / NO_LUT_BFHEATING).  Returns 0,
+ *   ARTIS_ERR_BAD_ARGUMENT for a bad argument (a hash that is not 32 characters among them) or a failed write.
+ * read: returns 1 when the file matches and was read into `tables` (a NULL corrphotoioncoeff / bfheating_coeff array
+ *   skips that column); *have_* (optional) are 0 when that column holds a negative value, i.e. the table is absent,
+ *   where the reference aborts if it needs the table.  Returns 0 for "no match", where the reference recalculates:
+ *   no such file, a different hash, MINTEMP / MAXTEMP (compared as the floats the reference reads) / TABLESIZE /
+ *   nlines, or ion line -- `tables` may then hold nothing useful.  ARTIS_ERR_BAD_ARGUMENT: a bad argument or a file
+ *   that ends or fails to parse where the reference's assert_always would stop. */
+int artis_write_ratecoeff_dat(const char *filename, const artis_atomic_tables *atomic,
+                              const artis_ratecoeff_out *tables, const char *const md5[3]);
+int artis_read_ratecoeff_dat(const char *filename, const artis_atomic_tables *atomic, const char *const md5[3],
+                             artis_ratecoeff_out *tables, int32_t *have_corrphotoioncoeff,
+                             int32_t *have_bfheating_coeff);
+
 #ifdef __cplusplus
 }
 #endif
