@@ -34,7 +34,12 @@ ABI_SYMBOLS = [
     "artis_gpu_solve_temperatures", "artis_gpu_last_te_ms", "artis_gpu_prepare_temperatures",
     "artis_gpu_update_grid_nlte", "artis_gpu_last_nlte_ms", "artis_gpu_table_info", "artis_gpu_vpkt_last_drains",
     "artis_gpu_ratecoeff_tables", "artis_gpu_last_ratecoeff_ms",
+    "artis_gpu_cell_table", "artis_gpu_cell_ma_keys",
 ]
+
+# artis_gpu_cell_table's table numbers (ARTIS_CELL_TABLE_* of include/artis_gpu.h), in order
+CELL_TABLES = ("ionpop", "ffsum", "pops", "popsT", "bfcell", "corrphot", "corrphotT", "cooling", "nt_cum",
+               "nt_total", "linecoef", "linecoef_neg", "marates", "cell_mgi")
 
 _gpu_lib = None
 
@@ -78,6 +83,8 @@ def gpu_lib():
         L.artis_gpu_last_precompute_ms.restype = C.c_double
         L.artis_gpu_last_work_counts.argtypes = [vp]
         L.artis_gpu_table_info.argtypes = [vp]
+        L.artis_gpu_cell_table.argtypes = [C.c_int, vp, vp]
+        L.artis_gpu_cell_ma_keys.argtypes = [C.c_int, vp, vp, vp]
         L.artis_gpu_vpkt_last_drains.restype = C.c_int64
         L.artis_gpu_last_error.restype = C.c_char_p
         L.artis_gpu_last_rounds.restype = C.c_int64
@@ -232,6 +239,40 @@ class Engine:
         return dict(zip(("cells", "linecoef_rows", "linecoef_bytes", "macache_rows", "macache_bytes",
                          "marates_bytes", "ma_jumps_recorded", "ma_jumps", "ma_level_records",
                          "ma_level_bytes", "ma_pool_bytes"), (int(x) for x in w)))
+
+    def cell_table(self, name):
+        """One per-cell table of the uploaded cell state (artis_gpu_cell_table; name: one of CELL_TABLES) as it lies
+        on the device, indexed by non-empty cell index: float64 [rows, cols] ("bfcell": [cells, nbf, 2];
+        "linecoef_neg": the int flag; "cell_mgi": int32 [cells], each cell's model-grid index), None for a table
+        the configuration does not build."""
+        t = CELL_TABLES.index(name)
+        shape = np.zeros(2, dtype=np.int64)
+        self._check(self.lib.artis_gpu_cell_table(t, None, shape.ctypes.data), "cell_table")
+        if shape[0] == 0:
+            return None
+        is_int = name in ("linecoef_neg", "cell_mgi")
+        out = np.zeros((int(shape[0]), int(shape[1])), dtype=np.int32 if is_int else np.float64)
+        self._check(self.lib.artis_gpu_cell_table(t, out.ctypes.data, shape.ctypes.data), "cell_table")
+        if name == "linecoef_neg":
+            return int(out[0, 0])
+        if name == "cell_mgi":
+            return out[:, 0]
+        return out.reshape(out.shape[0], -1, 2) if name == "bfcell" else out
+
+    def cell_ma_keys(self, k):
+        """The macro-atom key records of non-empty cell k (artis_gpu_cell_ma_keys): (keys uint32 [keys per cell],
+        has_record bool [nlevels], hi_only, separator mismatches), the levels one after another, each in the order
+        [9 actions | down-same nd | up-same nu | rad_deexc nd | rad_recomb nr | internal_down_lower nr |
+        internal_up_higher nt]; None when the engine holds no records."""
+        info = np.zeros(4, dtype=np.int64)
+        self._check(self.lib.artis_gpu_cell_ma_keys(int(k), None, None, info.ctypes.data), "cell_ma_keys")
+        if info[0] == 0:
+            return None
+        keys = np.zeros(int(info[0]), dtype=np.uint32)
+        has = np.zeros(int(info[1]), dtype=np.uint8)
+        self._check(self.lib.artis_gpu_cell_ma_keys(int(k), keys.ctypes.data, has.ctypes.data, info.ctypes.data),
+                    "cell_ma_keys")
+        return keys, has.astype(bool), bool(info[2]), int(info[3])
 
     def spectrum(self, nnubins=1000, nprocs=1):
         """Device-binned spectrum [ntstep, nnubins] and light curves (lum, lumcmf) of the resident packets."""

@@ -1786,6 +1786,121 @@ int artis_gpu_table_info(int64_t out[ARTIS_TABLE_INFO_COUNT]) {
   return 0;
 }
 
+// Introspection (tests): one per-cell table of the current cell state, copied to the host as it lies in HBM.
+int artis_gpu_cell_table(int table, void *dst, int64_t shape[2]) {
+  if (!G.initialised || !G.have_cells) return ARTIS_ERR_NOT_INITIALISED;
+  if (!shape) {
+    G.last_error = "cell_table: shape is NULL";
+    return ARTIS_ERR_BAD_ARGUMENT;
+  }
+  const DevCells &C = G.K.C;
+  const DevTab &T = G.K.T;
+  const int64_t n = C.n_nonempty;
+  const void *src = nullptr;
+  int64_t rows = 0, cols = 0;
+  size_t elem = sizeof(double);
+  switch (table) {
+    case ARTIS_CELL_TABLE_IONPOP: src = C.ionpop, rows = n, cols = T.nions_total; break;
+    case ARTIS_CELL_TABLE_FFSUM: src = C.ffsum, rows = n, cols = 1; break;
+    case ARTIS_CELL_TABLE_POPS: src = C.pops, rows = n, cols = T.nlevels_total; break;
+    case ARTIS_CELL_TABLE_POPST: src = C.popsT, rows = T.nlevels_total, cols = n; break;
+    case ARTIS_CELL_TABLE_BFCELL: src = C.bfcell, rows = n, cols = 2 * (int64_t)T.nbf; break;
+    case ARTIS_CELL_TABLE_CORRPHOT: src = C.corrphot, rows = n, cols = T.ntargets_total; break;
+    case ARTIS_CELL_TABLE_CORRPHOTT: src = C.corrphotT, rows = T.ntargets_total, cols = n; break;
+    case ARTIS_CELL_TABLE_COOLING: src = C.cooling, rows = n, cols = T.ncoolingterms; break;
+    case ARTIS_CELL_TABLE_NT_CUM: src = G.K.R.nt_on ? C.nt_cum : nullptr, rows = n, cols = T.nions_total; break;
+    case ARTIS_CELL_TABLE_NT_TOTAL: src = G.K.R.nt_on ? C.nt_total : nullptr, rows = n, cols = 1; break;
+    case ARTIS_CELL_TABLE_LINECOEF: src = C.linecoef, rows = C.linecoef_rows, cols = C.linecoef_stride; break;
+    case ARTIS_CELL_TABLE_LINECOEF_NEG: src = C.linecoef_neg, rows = 1, cols = 1, elem = sizeof(int32_t); break;
+    case ARTIS_CELL_TABLE_MARATES:
+      src = C.marates, rows = n, cols = (int64_t)T.nlevels_total * ARTIS_MA_ACTION_COUNT;
+      break;
+    case ARTIS_CELL_TABLE_CELL_MGI: src = C.ne_mgi, rows = n, cols = 1, elem = sizeof(int32_t); break;
+    default:
+      G.last_error = "cell_table: unknown table";
+      return ARTIS_ERR_BAD_ARGUMENT;
+  }
+  if (!src || rows <= 0 || cols <= 0) rows = cols = 0;  // a table this configuration does not build
+  shape[0] = rows;
+  shape[1] = cols;
+  if (!dst || !rows) return 0;
+  HIPCHK(hipStreamSynchronize(G.stream));
+  HIPCHK(hipMemcpy(dst, src, (size_t)rows * (size_t)cols * elem, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// Introspection (tests): the macro-atom key records of non-empty cell k, decoded with the kernels' own layout
+// functions (ma_layout / ma_rec_pos) into k_marates' scratch order, level ul's keys at G.h_dbl_off[ul].
+int artis_gpu_cell_ma_keys(int k, uint32_t *keys, uint8_t *has_record, int64_t info[ARTIS_MA_KEYS_INFO_COUNT]) {
+  if (!G.initialised || !G.have_cells) return ARTIS_ERR_NOT_INITIALISED;
+  const DevCells &C = G.K.C;
+  const int nl = G.K.T.nlevels_total;
+  if (!info || k < 0 || k >= C.n_nonempty) {
+    G.last_error = "cell_ma_keys: info is NULL or the cell index is out of range";
+    return ARTIS_ERR_BAD_ARGUMENT;
+  }
+  const bool have = C.ma_key && (C.ma_level_mode || C.ma_rows > 0);
+  info[0] = have ? G.h_dbl_off[nl] : 0;
+  info[1] = nl;
+  info[2] = C.ma_hi_only;
+  info[3] = 0;
+  if (!have || !keys || !has_record) return 0;
+  HIPCHK(hipStreamSynchronize(G.stream));
+  // the cell's records on the host: rec0[ul] the first 16-bit position of level ul's record in h, -1 without one
+  std::vector<uint16_t> h;
+  std::vector<int64_t> rec0(nl, -1);
+  if (!C.ma_level_mode) {
+    h.resize((size_t)C.ma_key_stride);
+    HIPCHK(hipMemcpy(h.data(), C.ma_key + (int64_t)k * C.ma_key_stride, h.size() * 2, hipMemcpyDeviceToHost));
+    for (int ul = 0; ul < nl; ul++) rec0[ul] = G.h_ma_meta[ul].rec_off;
+  } else {
+    std::vector<uint32_t> lptr(nl);
+    HIPCHK(hipMemcpy(lptr.data(), G.d_ma_lptr + (int64_t)k * nl, (size_t)nl * 4, hipMemcpyDeviceToHost));
+    std::vector<std::pair<uint32_t, int>> recs;  // (first pool line, level), runs of adjacent records in one copy
+    for (int ul = 0; ul < nl; ul++)
+      if (lptr[ul] != MA_NOLINE && G.h_rec_lines[ul]) recs.push_back({lptr[ul], ul});
+    std::sort(recs.begin(), recs.end());
+    for (size_t a = 0; a < recs.size();) {
+      size_t b = a;
+      uint64_t end = recs[a].first;
+      while (b < recs.size() && recs[b].first == end) end += G.h_rec_lines[recs[b++].second];
+      if (end > G.ma_pool_lines) {
+        G.last_error = "cell_ma_keys: a record lies outside the pool";
+        return ARTIS_ERR_BAD_ARGUMENT;
+      }
+      const size_t at = h.size(), cnt = (size_t)(end - recs[a].first) * 64;
+      h.resize(at + cnt);
+      HIPCHK(hipMemcpy(h.data() + at, C.ma_key + (size_t)recs[a].first * 64, cnt * 2, hipMemcpyDeviceToHost));
+      for (size_t r = a; r < b; r++) rec0[recs[r].second] = (int64_t)(at + (size_t)(recs[r].first - recs[a].first) * 64);
+      a = b;
+    }
+  }
+  int64_t sep_bad = 0;
+  for (int ul = 0; ul < nl; ul++) {
+    const MaMeta &m = G.h_ma_meta[ul];
+    const int64_t len = G.h_dbl_off[ul + 1] - G.h_dbl_off[ul];
+    uint32_t *out = keys + G.h_dbl_off[ul];
+    has_record[ul] = rec0[ul] >= 0;
+    if (rec0[ul] < 0) {
+      for (int64_t p = 0; p < len; p++) out[p] = 0;
+      continue;
+    }
+    const MaLayout L = ma_layout(m.nd, m.nu, m.nr, m.nt);
+    const uint16_t *rec = h.data() + rec0[ul];
+    auto key_at = [&](int pos) {
+      return ((uint32_t)rec[pos] << 16) | (C.ma_hi_only ? 0u : (uint32_t)rec[L.hot + pos]);
+    };
+    for (int64_t p = 0; p < len; p++) {
+      int sp;
+      const int rp = ma_rec_pos(L, (int)p, m.nd, m.nu, &sp);
+      out[p] = key_at(rp);
+      if (sp >= 0 && key_at(sp) != out[p]) sep_bad++;
+    }
+  }
+  info[3] = sep_bad;
+  return 0;
+}
+
 int artis_gpu_last_work_counts(int64_t out[ARTIS_WORK_COUNT]) {
   for (int k = 0; k < ARTIS_WORK_COUNT; k++) out[k] = G.last_work[k];
   return 0;
@@ -1990,6 +2105,7 @@ static int upload_atomic_tables(const artis_atomic_tables *a, const artis_run_pa
   rc |= dupload(&T.down_target, ma.down_target);
   rc |= dupload(&T.up_target, ma.up_target);
   G.h_dbl_off = ma.dbl_off;
+  G.h_ma_meta = ma.meta;
   G.ma_key_stride = ma.key_stride;
   G.ma_cache_ok = ma.cache_ok;
   rc |= dupload(&T.allcont_nu_edge, a->allcont_nu_edge, nb);

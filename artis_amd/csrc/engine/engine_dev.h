@@ -310,12 +310,13 @@ struct DevCells {
   // hot part: a typical jump reads one 128-byte line of them) and their low halves after (read only when the high
   // half cannot decide a comparison).  A search compares the uniform draw with the keys; a key within rounding of
   // the draw leaves the comparison undecided and the jump is made with the exact sums (ma_jump_exact) -- the
-  // selections are the reference's linear-scan choices either way.  The two arrays of the internal same-ion
-  // jumps (most jumps) come first, in Eytzinger (BFS) order, their top entries on the record's first line
-  // (ma_rec_pos above):
-  //   [9 action keys | internal_down_same (nd, Eytzinger) | internal_up_same (nu, Eytzinger) | rad_deexc (nd) |
-  //    rad_recomb (nr) | internal_down_lower (nr) | internal_up_higher (nt)]  high halves, then the same
-  //   positions' low halves; the record padded to a multiple of 64 keys
+  // selections are the reference's linear-scan choices either way.  The record's positions are ma_layout /
+  // ma_rec_pos above: the 9 action keys and the two arrays of the internal same-ion jumps (most jumps) on the
+  // first line, every array in list order; a same-ion array that does not fit its share of that line lies in
+  // 64-key blocks on the following lines, and the first line holds the last key of each block (separators) and
+  // the array's last keys (suffix).  Then rad_deexc (nd) | rad_recomb (nr) | internal_down_lower (nr) |
+  // internal_up_higher (nt).  The high halves of all positions come first, then the same positions' low halves
+  // (level mode: none, ma_hi_only); the record is padded to a multiple of 64 keys.
   uint16_t *ma_key;    // [n_nonempty * ma_key_stride], or nullptr
   int64_t ma_key_stride;
   int32_t have_macache;  // ma_rows > 0

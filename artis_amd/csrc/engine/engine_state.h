@@ -224,6 +224,7 @@ struct Engine {
   int64_t ma_key_stride = 0;          // 16-bit keys per cell block of the macro-atom cache
   bool ma_cache_ok = true;             // the atomic data fit the cache's record layout (engine_dev.h ma_layout)
   std::vector<int64_t> h_dbl_off;     // per level: offset (doubles) of its exact sums in the k_marates scratch
+  std::vector<MaMeta> h_ma_meta;      // host copy of DevTab::ma_meta (artis_gpu_cell_ma_keys decodes records with it)
   double *d_marec_scratch = nullptr;  // k_marates output, [position][cell] per level (k_mapack input)
   // macro-atom key records (DevCells::ma_row / ma_bin): row of each cell (row mode), the cell of each bin
   int32_t *d_ma_row = nullptr, *d_ma_bin = nullptr, *d_ma_bincell = nullptr;

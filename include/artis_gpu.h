@@ -503,6 +503,43 @@ int artis_gpu_last_work_counts(int64_t out[ARTIS_WORK_COUNT]);
  * never changes a result. */
 #define ARTIS_TABLE_INFO_COUNT 11
 int artis_gpu_table_info(int64_t out[ARTIS_TABLE_INFO_COUNT]);
+/* Read-back of the per-cell tables artis_gpu_upload_cellstate built (ABI 12; introspection for tests, a few
+ * synchronous copies, never on the hot path).  All are indexed by non-empty cell index k.  shape[0] x shape[1]
+ * elements are returned, doubles but for LINECOEF_NEG (one int32_t) and CELL_MGI (int32_t [cells], the model-grid
+ * index of each non-empty cell); dst == NULL only reports the shape, and a table
+ * the configuration does not build (NT_* without the non-thermal option, MARATES outside level mode, LINECOEF
+ * without a row) has shape 0 x 0.  IONPOP [cells x nions_total], FFSUM [cells], POPS [cells x nlevels_total], POPST
+ * its level-major copy, BFCELL [cells x 2 nbf] (pairs: the level population if the continuum is included else 0,
+ * the departure ratio), CORRPHOT [cells x ntargets_total], CORRPHOTT its transpose, COOLING [cells x ncoolingterms],
+ * NT_CUM [cells x nions_total], NT_TOTAL [cells], LINECOEF [linecoef_rows x linecoef_stride] padding included,
+ * MARATES [cells x nlevels_total * ARTIS_MA_ACTION_COUNT].  ARTIS_ERR_NOT_INITIALISED before the first
+ * artis_gpu_upload_cellstate. */
+enum {
+  ARTIS_CELL_TABLE_IONPOP = 0,
+  ARTIS_CELL_TABLE_FFSUM,
+  ARTIS_CELL_TABLE_POPS,
+  ARTIS_CELL_TABLE_POPST,
+  ARTIS_CELL_TABLE_BFCELL,
+  ARTIS_CELL_TABLE_CORRPHOT,
+  ARTIS_CELL_TABLE_CORRPHOTT,
+  ARTIS_CELL_TABLE_COOLING,
+  ARTIS_CELL_TABLE_NT_CUM,
+  ARTIS_CELL_TABLE_NT_TOTAL,
+  ARTIS_CELL_TABLE_LINECOEF,
+  ARTIS_CELL_TABLE_LINECOEF_NEG,
+  ARTIS_CELL_TABLE_MARATES,
+  ARTIS_CELL_TABLE_CELL_MGI,
+  ARTIS_CELL_TABLE_COUNT
+};
+int artis_gpu_cell_table(int table, void *dst, int64_t shape[2]);
+/* The macro-atom key records of non-empty cell k, decoded from the record layout into one list per level,
+ * [9 action keys | down-same nd | up-same nu | rad_deexc nd | rad_recomb nr | internal_down_lower nr |
+ * internal_up_higher nt], the levels one after another: key = high half << 16 | low half.  info[0] keys per cell
+ * (0: no records), info[1] levels, info[2] 1 if the records hold no low halves (they read 0), info[3] separator
+ * slots of the records' first lines whose stored copy differs from the key it duplicates.  has_record[level] is 0
+ * for a level without a record in this cell (level mode; its keys read 0).  keys == NULL only fills info[0..2]. */
+#define ARTIS_MA_KEYS_INFO_COUNT 4
+int artis_gpu_cell_ma_keys(int k, uint32_t *keys, uint8_t *has_record, int64_t info[ARTIS_MA_KEYS_INFO_COUNT]);
 /* Emergent spectrum and light curve of the escaped r-packets among the resident packets, binned on the device:
  * the binning of write_partial_lightcurve_spectra (spectrum.cc:641-721) -- add_to_spec (spectrum.cc:339-362,
  * angle-averaged, no emission-resolved columns) and add_to_lc_res (light_curve.cc:34-54) -- over
@@ -859,7 +896,7 @@ int artis_gpu_ratecoeff_tables(int device, const artis_atomic_tables *atomic, co
                                artis_ratecoeff_out *out);
 double artis_gpu_last_ratecoeff_ms(void);  /* device time (ms) of the last call's kernel (k_ratecoeff_lut) */
 
-#define ARTIS_GPU_ABI_VERSION 11 /* 2: gamma / pellet / non-thermal path (artis_gamma_spectra and appended fields);
+#define ARTIS_GPU_ABI_VERSION 12 /* 2: gamma / pellet / non-thermal path (artis_gamma_spectra and appended fields);
                                     3: virtual packets (artis_vpkt_params / artis_vpkt_result);
                                     4: artis_run_params.excitation_temperature;
                                     5: host estimator block pack/unpack, RCCL communicator + all-reduce;
@@ -876,7 +913,9 @@ double artis_gpu_last_ratecoeff_ms(void);  /* device time (ms) of the last call'
                                        rpkt_emiss for do_rlc_est 1 / 2; artis_gpu_table_info's level-mode entries;
                                        (still 11, an appended entry point breaks no caller) artis_gpu_spectra_res
                                        and artis_spectra_res_request; artis_gpu_line_trace and its structs;
-                                       artis_gpu_ratecoeff_tables and its structs */
+                                       artis_gpu_ratecoeff_tables and its structs;
+                                   12: artis_gpu_cell_table, artis_gpu_cell_ma_keys (read-back of the per-cell
+                                       tables) */
 int artis_gpu_abi_version(void);
 
 #ifdef __cplusplus

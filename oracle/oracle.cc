@@ -3740,6 +3740,81 @@ double oracle_corrphotoioncoeff(const artis_atomic_tables *at, const artis_geome
   return std::isfinite(r) ? r : bad;
 }
 
+// What the packets of model cell mgi read from the cell history at timestep nts, for tests/cell_tables_ref.py:
+// calculate_levelpop of every level (pops [nlevels_total]); the cumulative cooling list as do_kpkt builds it, ion by
+// ion from the running sum of cooling_contrib_ion (cooling [ncoolingterms]); calculate_macroatom_transitionrates
+// of every level: the nine totals (processrates [nlevels_total * 9]) and the running sums of the three individ_*
+// arrays it keeps (down_same, rad_deexc [sum ndowntrans]; up_same [sum nuptrans], at the transitions' offsets).
+int oracle_cell_tables(const artis_atomic_tables *at, const artis_geometry *geom, const artis_cell_state *cs,
+                       const artis_run_params *rp, int nts, int mgi, double *pops, double *cooling,
+                       double *processrates, double *cum_down_same, double *cum_rad_deexc, double *cum_up_same) {
+  if (mgi < 0 || mgi >= geom->npts_model || nts < 0 || nts >= geom->ntstep) return ARTIS_ERR_BAD_ARGUMENT;
+  if ((rp->nlte_pops_on && (!at->ion_nlevels_nlte || !at->ion_first_nlte || !cs->nlte_pops)) ||
+      (rp->multibin_radfield && (at->radfield_nbins <= 0 || !at->radfield_nu_upper || !cs->radfield_bin_TR ||
+                                 !cs->radfield_bin_W)) ||
+      (rp->detailed_bf_estimators && !cs->bfrate_estimator) || (rp->nt_on && !cs->nt_ionization_ratecoeff))
+    return ARTIS_ERR_BAD_ARGUMENT;
+  Ctx c;
+  c.at = at;
+  c.g = geom;
+  c.cs = cs;
+  c.rp = *rp;
+  c.gs = nullptr;
+  c.T_step_log = (log(at->maxtemp) - log(at->mintemp)) / (at->tablesize - 1.);
+  c.nts = nts;
+  c.minpop = rp->minpop > 0. ? rp->minpop : 1e-30;
+  size_t ndown = 0, nup = 0, ntg = 0;
+  for (int lv = 0; lv < at->nlevels_total; lv++) {
+    ndown += at->level_ndowntrans[lv];
+    nup += at->level_nuptrans[lv];
+    ntg += at->level_nphixstargets[lv];
+  }
+  c.slot_allcont.assign(ntg + 1, -1);
+  for (int ib = 0; ib < at->nbfcontinua; ib++) {
+    const int u = at->ion_uniqueleveloffset[at->elem_uniqueionoffset[at->allcont_element[ib]] + at->allcont_ion[ib]] +
+                  at->allcont_level[ib];
+    c.slot_allcont[at->level_phixstargets_offset[u] + at->allcont_phixstargetindex[ib]] = ib;
+  }
+  ThreadCache tc;
+  tc.pops.assign(at->nlevels_total, 0.);
+  tc.departureratios.assign(at->nbfcontinua, -1.);
+  tc.processrates.assign((size_t)at->nlevels_total * 9, -99.);
+  tc.individ_rad_deexc.assign(ndown, 0.);
+  tc.individ_internal_down_same.assign(ndown, 0.);
+  tc.individ_internal_up_same.assign(nup, 0.);
+  tc.corrphotoioncoeff.assign(ntg + 1, -99.);
+  tc.cooling_contrib.assign(at->ncoolingterms, -99.);
+  cellhistory_reset(c, tc, mgi);
+  for (int lv = 0; lv < at->nlevels_total; lv++) pops[lv] = tc.pops[lv];
+  double coolingsum = 0.;
+  for (int e = 0; e < at->nelements; e++)
+    for (int i = 0; i < get_nions(c, e); i++) {
+      const int ui = uion(c, e, i);
+      calculate_kpkt_rates_ion(c, tc, mgi, e, i, at->ion_coolingoffset[ui], coolingsum);
+      coolingsum += cs->cooling_contrib_ion[(size_t)mgi * at->nions_total + ui];
+    }
+  for (int k = 0; k < at->ncoolingterms; k++) cooling[k] = tc.cooling_contrib[k];
+  const double t_mid = geom->ts_mid[nts];
+  for (int e = 0; e < at->nelements; e++)
+    for (int i = 0; i < get_nions(c, e); i++)
+      for (int l = 0; l < get_nlevels(c, e, i); l++) {
+        calculate_macroatom_transitionrates(c, tc, mgi, e, i, l, t_mid);
+        const int ul = ulev(c, e, i, l);
+        double sd = 0., sr = 0., su = 0.;
+        for (int k = 0; k < at->level_ndowntrans[ul]; k++) {
+          const size_t j = (size_t)at->level_downtrans_offset[ul] + k;
+          cum_down_same[j] = sd += tc.individ_internal_down_same[j];
+          cum_rad_deexc[j] = sr += tc.individ_rad_deexc[j];
+        }
+        for (int k = 0; k < at->level_nuptrans[ul]; k++) {
+          const size_t j = (size_t)at->level_uptrans_offset[ul] + k;
+          cum_up_same[j] = su += tc.individ_internal_up_same[j];
+        }
+      }
+  for (size_t k = 0; k < (size_t)at->nlevels_total * 9; k++) processrates[k] = tc.processrates[k];
+  return 0;
+}
+
 // ---- unit hooks for tests/ ---------------------------------------------------------------------------------
 // Philox4x32-10 block (known-answer tests against the published Random123 vectors)
 void oracle_philox4x32_10(uint32_t ctr[4], uint32_t k0, uint32_t k1) { artis_philox4x32_10(ctr, k0, k1); }

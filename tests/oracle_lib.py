@@ -73,6 +73,30 @@ def update_packets_vpkt(model, nts, packets, vcfg, vout=None, est=None, nthreads
     return est, vout, work
 
 
+def cell_tables(model, nts, mgi, params=None):
+    """What the oracle's packets read from the cell history of model cell mgi at timestep nts (oracle_cell_tables):
+    {"pops" [nlevels], "cooling" [ncoolingterms], "processrates" [nlevels, 9], "cum_down_same", "cum_rad_deexc"
+    [sum ndowntrans], "cum_up_same" [sum nuptrans]} -- the last three the running sums of the individ_* arrays at the
+    transitions' offsets."""
+    L = lib()
+    L.oracle_cell_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ffi.RunParams), C.c_int,
+                                     C.c_int] + [C.c_void_p] * 6
+    L.oracle_cell_tables.restype = C.c_int
+    a = ffi.AtomicTables.from_address(model.atomic)
+    nl = model.nlevels_total
+    i32 = lambda p: np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32)), (nl,))  # noqa: E731
+    ndown, nup = int(i32(a.level_ndowntrans).sum()), int(i32(a.level_nuptrans).sum())
+    out = {"pops": np.zeros(nl), "cooling": np.zeros(model.ncoolingterms), "processrates": np.zeros((nl, 9)),
+           "cum_down_same": np.zeros(ndown), "cum_rad_deexc": np.zeros(ndown), "cum_up_same": np.zeros(nup)}
+    p = params if params is not None else model.params
+    rc = L.oracle_cell_tables(model.atomic, model.geometry, model.cellstate, C.byref(p), int(nts), int(mgi),
+                              *(out[k].ctypes.data for k in ("pops", "cooling", "processrates", "cum_down_same",
+                                                             "cum_rad_deexc", "cum_up_same")))
+    if rc != 0:
+        raise RuntimeError(f"oracle_cell_tables -> {rc}")
+    return out
+
+
 def spectrum(model, packets, nnubins=1000, nprocs=1):
     """Oracle binning of write_partial_lightcurve_spectra (oracle/oracle.cc: oracle_spectrum)."""
     L = lib()

@@ -98,7 +98,7 @@ def test_library_exports_every_declared_symbol():
 
 def test_library_loads_without_gpu_and_reports_version():
     lib = C.CDLL(GPU_SO)
-    assert lib.artis_gpu_abi_version() == 11
+    assert lib.artis_gpu_abi_version() == 12
     lib.artis_gpu_last_error.restype = C.c_char_p
     assert lib.artis_gpu_last_error() is not None
 
@@ -107,6 +107,20 @@ def test_engine_refuses_uninitialised_calls():
     lib = C.CDLL(GPU_SO)
     lib.artis_gpu_update_packets_resident.argtypes = [C.c_int, C.c_int]
     assert lib.artis_gpu_update_packets_resident(0, 0) == -1  # ARTIS_ERR_NOT_INITIALISED
+
+
+def test_cell_table_readback_refuses_uninitialised_calls():
+    """artis_gpu_cell_table / artis_gpu_cell_ma_keys before any cell state: ARTIS_ERR_NOT_INITIALISED, nothing
+    written."""
+    lib = C.CDLL(GPU_SO)
+    vp = C.c_void_p
+    lib.artis_gpu_cell_table.argtypes = [C.c_int, vp, vp]
+    lib.artis_gpu_cell_ma_keys.argtypes = [C.c_int, vp, vp, vp]
+    shape = np.full(2, -7, dtype=np.int64)
+    info = np.full(4, -7, dtype=np.int64)
+    assert lib.artis_gpu_cell_table(2, None, shape.ctypes.data) == -1
+    assert lib.artis_gpu_cell_ma_keys(0, None, None, info.ctypes.data) == -1
+    assert (shape == -7).all() and (info == -7).all()
 
 
 def test_raw_tmp_packet_file_roundtrip(tmp_path, small_model):

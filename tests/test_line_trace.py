@@ -15,7 +15,7 @@ def test_library_exports_the_entry_point_and_keeps_the_abi():
     out = subprocess.run(["nm", "-D", "--defined-only", GPU_SO], check=True, capture_output=True, text=True).stdout
     assert "artis_gpu_line_trace" in {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
     lib = C.CDLL(GPU_SO)
-    assert lib.artis_gpu_abi_version() == 11
+    assert lib.artis_gpu_abi_version() == 12
     lib.artis_gpu_line_trace.argtypes = [C.POINTER(ffi.LineTraceRequest), C.POINTER(ffi.LineTraceOut)]
     arr = ffi.LineTraceArrays(10, 1)
     req = ffi.line_trace_request([T.REGIONS[0]], T.NNUBINS)
