@@ -1319,6 +1319,7 @@ int run_wavefront(int64_t n, int nts, double t2) {
                !(G.knob.ma_bin_blk && G.K.C.n_nonempty + 1 <= MA_BIN_LDS);
   // k_ma parks a long launch's tail walks (row mode; only with tickets, WaveState::ma_park)
   W.ma_park = (W.ma_tick && !G.K.C.ma_level_mode) ? G.knob.ma_park : 0;
+  W.fin_gather = G.knob.fin_gather ? 1 : 0;
   const unsigned grid = (unsigned)G.wave_grid;
   if (int rc = sync_ctx()) return rc;
   G.tev_used = 0;
@@ -1461,14 +1462,20 @@ int run_wavefront(int64_t n, int nts, double t2) {
       HIPCHK(hipMemsetAsync(W.ctr + 2 * QX, 0, 2 * sizeof(uint32_t), G.stream));
     }
     {  // the walks' deactivations -> R / K
+      auto launch_finish = [&]() {
+        if (W.fin_gather)
+          k_ma_finish<true><<<grid / 4, WAVE_BLOCK, 0, G.stream>>>(G.d_ctx, W, G.d_soa, n, nts, t2);
+        else
+          k_ma_finish<false><<<grid / 4, WAVE_BLOCK, 0, G.stream>>>(G.d_ctx, W, G.d_soa, n, nts, t2);
+      };
       TSTART(6);
       if (G.K.V.on)
         HIPCHK(hipMemcpyAsync(G.d_qsnap, W.ctr + 2 * QF, sizeof(uint32_t), hipMemcpyDeviceToDevice, G.stream));
-      k_ma_finish<<<grid / 4, WAVE_BLOCK, 0, G.stream>>>(G.d_ctx, W, G.d_soa, n, nts, t2);
+      launch_finish();
       TEND(6);
       if (int rc = vpkt_drain(QF, [&]() -> int {
             TSTART(6);
-            k_ma_finish<<<grid / 4, WAVE_BLOCK, 0, G.stream>>>(G.d_ctx, W, G.d_soa, n, nts, t2);
+            launch_finish();
             TEND(6);
             return 0;
           }))

@@ -44,6 +44,11 @@ namespace {
 //                       |                |                         |   0: 1500, 8: 1285, 16: 1254, 24: 1237, 32: 1230, 40: 1227,
 //                       |                |                         |   48: 1240, 64: 1243; the step 2636 -> 2412 ms at 32
 //                       |                |                         |   (profiles/r7_ma_park_ab.txt)
+//   FIN_GATHER=0        | on             | '0' off                 | k_ma_finish gathers a wave's R / K appends in LDS and adds
+//                       |                |                         |   to the queue counter once per ~960 entries, not once per
+//                       |                |                         |   pass: adds to one word take 11.35 ns each device-wide
+//                       |                |                         |   (tools/atomrate.hip); k_ma_finish per 1e7 bench step
+//                       |                |                         |   199 -> 161 ms, the step 2412 -> 2369 (profiles/r8_pkt_coop_ab.txt)
 //   MA_OCC=8            | 1              | '8': 8, else 1          | k_ma minimum waves per SIMD (launch bounds)
 //   MA_WAVES=<w>        | 4              | atoi in 1..8, else 4    | k_ma blocks per CU: fewer concurrent walks thrash the
 //                       |                |                         |   caches less, the walk is bound by the memory system (1e7
@@ -84,6 +89,7 @@ struct Knobs {
   bool ma_bin_blk = true;   // few cells: block-local M-queue binning (off: per-entry atomics)
   int refill_min = 32, refill_ma = 12;
   int ma_park = MA_PARK_DEFAULT;  // WaveState::ma_park
+  bool fin_gather = true;   // WaveState::fin_gather
   int ma_occ = 1;    // k_ma minimum waves per SIMD (launch bounds): 1 or 8
   int ma_waves = 4;  // k_ma blocks per CU
   int coop_max = 64;
@@ -131,6 +137,7 @@ inline Knobs read_knobs() {
   k.refill_min = lanes("ARTIS_GPU_REFILL", 32);
   k.refill_ma = lanes("ARTIS_GPU_REFILL_MA", 12);
   if (const char *e = getenv("ARTIS_GPU_MA_PARK")) k.ma_park = std::max(0, std::min(64, atoi(e)));
+  k.fin_gather = !first_is("ARTIS_GPU_FIN_GATHER", '0');
   k.ma_occ = first_is("ARTIS_GPU_MA_OCC", '8') ? 8 : 1;
   if (const char *e = getenv("ARTIS_GPU_MA_WAVES")) {
     const int v = atoi(e);

@@ -48,6 +48,8 @@ struct WaveState {
                        // for the next round (ARTIS_GPU_MA_PARK; 0: every walk runs to its end in this launch).  The
                        // parked walks are appended from slot 0 of the M queue with ctr[2 * QM + 1] as their count:
                        // only with tickets (k_ma then reads none of the queue's own arrays)
+  int fin_gather;      // 1: k_ma_finish gathers its queue appends in LDS (WaveOut; ARTIS_GPU_FIN_GATHER=0: one
+                       // append per loop pass)
   int coop_max;        // level mode: at most this many cooperative jumps per k_ma pass (the other lanes without a
                        // record wait for a later pass; ARTIS_GPU_MA_COOP_MAX, default 64 = all)
   // cell-sorted macro-atom tickets written by k_ma_scatter when the key cache is on (else nullptr): per slot
@@ -1231,6 +1233,41 @@ __global__ __launch_bounds__(64) void k_ma_exact(const Ctx *__restrict__ ctxp, W
   block_counters_flush(K, s_ctr, s_work);
 }
 
+// A wave's appends to one queue gathered in LDS and appended WAVE_OUT_CAP - 63 or more at a time: one atomic on the
+// queue's counter per flush instead of one per loop pass, and the indices written coalesced.  Returning adds from
+// many waves to one word are served one after the other, 11.35 ns each on MI355X however many waves wait
+// (tools/atomrate.hip, profiles/r8_pkt_coop_ab.txt); adds to words of their own take 0.05 ns.  k_ma_finish appended
+// to the R queue once per wave and loop pass: 76 500 adds to its counter per bench launch, 0.87 ms of serialised adds
+// in a launch of 1.18 ms; gathered, 199 -> 161 ms per bench step.  n is wave-uniform.  The queue's order changes; no
+// result depends on it.
+#ifndef WAVE_OUT_CAP
+#define WAVE_OUT_CAP 1024
+#endif
+typedef __attribute__((address_space(3))) int32_t lds_i32;
+struct WaveOut {
+  lds_i32 *buf;  // [WAVE_OUT_CAP]
+  uint32_t n;
+};
+DEVFN void wave_out_flush(const WaveState &W, int q, WaveOut &o) {
+  if (!o.n) return;
+  uint32_t base = 0;
+  if (lane_id() == 0) base = atomicAdd(&W.ctr[2 * q], o.n);
+  base = __shfl(base, 0, 64);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  for (uint32_t j = lane_id(); j < o.n; j += 64) W.q[q][base + j] = o.buf[j];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  o.n = 0;
+}
+DEVFN void wave_out_push(const WaveState &W, int q, WaveOut &o, bool pred, int32_t idx) {
+  const unsigned long long mask = __ballot(pred);
+  if (pred) o.buf[o.n + (uint32_t)__popcll(mask & ((1ull << lane_id()) - 1ull))] = idx;  // (< n + 64 <= WAVE_OUT_CAP)
+  o.n += (uint32_t)__popcll(mask);
+  if (o.n > WAVE_OUT_CAP - 64) wave_out_flush(W, q, o);
+}
+
 // macro-atom deactivations (the F queue, filled by k_ma and k_ma_exact): the deactivation branches of do_macroatom
 // (macroatom.cc:222-380) and its trailer (macroatom.cc:475-482) on the whole packet in registers, one packet per
 // lane, then -> R (bb / fb emission) or K (collisional deactivation).  Until round 4 k_rpkt / k_kpkt applied the
@@ -1241,6 +1278,8 @@ __global__ __launch_bounds__(64) void k_ma_exact(const Ctx *__restrict__ ctxp, W
 #ifndef MA_FINISH_MINW
 #define MA_FINISH_MINW 1  // waves per SIMD k_ma_finish is compiled for
 #endif
+// GATHER (WaveState::fin_gather, ARTIS_GPU_FIN_GATHER): the wave's R- and K-queue appends go through WaveOut.
+template <bool GATHER>
 __global__ __launch_bounds__(WAVE_BLOCK, MA_FINISH_MINW) void k_ma_finish(const Ctx *__restrict__ ctxp, WaveState W,
                                                           uint64_t *__restrict__ soa, int64_t n, int nts, double t2) {
   CTX_IN_LDS(ctxp)
@@ -1248,6 +1287,9 @@ __global__ __launch_bounds__(WAVE_BLOCK, MA_FINISH_MINW) void k_ma_finish(const 
   __shared__ unsigned long long s_work[ARTIS_WORK_COUNT];
   __shared__ double s_fbP[WAVE_BLOCK / 64][WAVE_FB_MAXP + 1];  // the waves' fb running sums (wave_select_continuum_nu)
   lds_double *fbP = (lds_double *)&s_fbP[threadIdx.x >> 6][0];
+  __shared__ int32_t s_out[GATHER ? WAVE_BLOCK / 64 : 1][2][GATHER ? WAVE_OUT_CAP : 1];  // the waves' gathered appends
+  WaveOut outR{(lds_i32 *)&s_out[GATHER ? threadIdx.x >> 6 : 0][0][0], 0u};
+  WaveOut outK{(lds_i32 *)&s_out[GATHER ? threadIdx.x >> 6 : 0][1][0], 0u};
   block_counters_init(s_ctr, s_work);
   LocalCounters L;
   L.ctr = &s_ctr[0];
@@ -1306,8 +1348,17 @@ __global__ __launch_bounds__(WAVE_BLOCK, MA_FINISH_MINW) void k_ma_finish(const 
       W.rng_n[idx] = x.rng.n;
       live = x.ok && p.prop_time < t2;
     }
-    wave_push(W, QR, live && p.type == ARTIS_TYPE_RPKT, idx);
-    wave_push(W, QK, live && (p.type == ARTIS_TYPE_KPKT || p.type == ARTIS_TYPE_PRE_KPKT), idx);
+    if constexpr (GATHER) {
+      wave_out_push(W, QR, outR, live && p.type == ARTIS_TYPE_RPKT, idx);
+      wave_out_push(W, QK, outK, live && (p.type == ARTIS_TYPE_KPKT || p.type == ARTIS_TYPE_PRE_KPKT), idx);
+    } else {
+      wave_push(W, QR, live && p.type == ARTIS_TYPE_RPKT, idx);
+      wave_push(W, QK, live && (p.type == ARTIS_TYPE_KPKT || p.type == ARTIS_TYPE_PRE_KPKT), idx);
+    }
+  }
+  if constexpr (GATHER) {  // (every exit of the loop comes here)
+    wave_out_flush(W, QR, outR);
+    wave_out_flush(W, QK, outK);
   }
   block_counters_flush(K, s_ctr, s_work);
 }

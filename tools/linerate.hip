@@ -2,7 +2,8 @@
 // Every lane follows a dependent chain of hops; a hop reads W 16-byte chunks (W = 1, 2, 4, 8: 16 B .. one
 // 128-byte line) at a random 128-byte-aligned offset of a table far larger than the Infinity Cache, and the
 // next offset hashes the loaded data.  Reported per W and resident waves per SIMD: G hops/s (= lines/s) and
-// the hop latency.  Usage: linerate [table GiB] [hops]
+// the hop latency; then the store mode (store_lane / store_coop below): G lines/s written.
+// Usage: linerate [table GiB] [hops]
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -70,6 +71,43 @@ __global__ __launch_bounds__(256) void chase_coop(const u32x4 *__restrict__ t, s
   if (acc == 42u) out[0] = acc;
 }
 
+// Stores of random 128-byte lines, no dependence between them (a store returns nothing to chase): per pass every
+// lane names one random line and the wave writes all 64.  store_lane: every lane writes the eight chunks of its own
+// line (each store instruction touches 64 lines); store_coop: eight lanes per line, eight lines per instruction,
+// the data staged chunk-major in LDS, the mirror of chase_coop.  Lines may repeat between waves (the data is
+// noise); within a pass a lane's line is its own.
+__global__ __launch_bounds__(256) void store_lane(u32x4 *__restrict__ t, size_t nlines, int hops) {
+  uint64_t x = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) * 0xD1B54A32D192ED03ull + 1;
+  for (int h = 0; h < hops; h++) {
+    x ^= x >> 29;
+    x *= 0xBF58476D1CE4E5B9ull;
+    u32x4 *p = t + (x % nlines) * 8;
+    const u32x4 v = {(unsigned)x, (unsigned)(x >> 32), (unsigned)h, threadIdx.x};
+#pragma unroll
+    for (int w = 0; w < 8; w++) p[w] = v;
+  }
+}
+__global__ __launch_bounds__(256) void store_coop(u32x4 *__restrict__ t, size_t nlines, int hops) {
+  __shared__ u32x4 s[4][8][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  uint64_t x = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) * 0xD1B54A32D192ED03ull + 1;
+  for (int h = 0; h < hops; h++) {
+    x ^= x >> 29;
+    x *= 0xBF58476D1CE4E5B9ull;
+    const unsigned line = (unsigned)(x % nlines);
+    const u32x4 v = {(unsigned)x, (unsigned)(x >> 32), (unsigned)h, threadIdx.x};
+#pragma unroll
+    for (int w = 0; w < 8; w++) s[wv][w][lane] = v;
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      const unsigned ls = (unsigned)__shfl((int)line, 8 * i + (lane >> 3), 64);
+      t[(size_t)ls * 8 + (lane & 7)] = s[wv][lane & 7][8 * i + (lane >> 3)];
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
 int main(int argc, char **argv) {
   const double gib = argc > 1 ? atof(argv[1]) : 32;
   const int hops = argc > 2 ? atoi(argv[2]) : 400;
@@ -106,6 +144,27 @@ int main(int argc, char **argv) {
         if (rep)
           printf("table %.0f GiB waves/SIMD %d bytes/hop %3d%s: %8.3f ms  %6.2f G hops/s  %6.3f TB/s  %6.2f us/hop\n", gib,
                  waves, 16 * wb, w ? "" : " coop", ms, all / ms / 1e6, all * 16 * wb / ms / 1e9, ms * 1e3 / hops);
+      }
+    }
+  }
+  // store mode: the same random lines written, one line per lane against eight lanes per line
+  for (int waves : {1, 2, 4, 8}) {
+    const int blocks = ncu * waves;
+    for (int coop : {0, 1}) {
+      for (int rep = 0; rep < 2; rep++) {
+        hipEventRecord(a);
+        if (coop)
+          store_coop<<<blocks, 256>>>(t, nlines, hops);
+        else
+          store_lane<<<blocks, 256>>>(t, nlines, hops);
+        hipEventRecord(b);
+        hipEventSynchronize(b);
+        float ms;
+        hipEventElapsedTime(&ms, a, b);
+        const double all = (double)blocks * 256 * hops;
+        if (rep)
+          printf("table %.0f GiB waves/SIMD %d store 128 B/line%s: %8.3f ms  %6.2f G lines/s  %6.3f TB/s\n", gib, waves,
+                 coop ? " coop" : "     ", ms, all / ms / 1e6, all * 128 / ms / 1e9);
       }
     }
   }
